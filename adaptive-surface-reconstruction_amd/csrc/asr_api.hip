@@ -937,11 +937,10 @@ struct Net {
 // The auxiliary context of the aggregation search: its own stream, arenas, counters.  Stream priority (option
 // "search_priority", fixed when the stream is made): highest by default -- the search is the longer of the two chains of the
 // geometry build (round 4: 9.6 -> 8.8 ms on its stream); it used to be lowest so that its large grids would not starve the
-// small kernels of the main chain.  HIP maps streams to a small number of hardware queues (GPU_MAX_HW_QUEUES, default 4)
+// small kernels of the main chain.  HIP maps streams to a small number of hardware queues
 // in creation order: a stream made after a library such as RCCL has made its own may share the main stream's queue, and
 // the two chains then run one after the other (geometry 13.5 instead of 9.5 ms at 10 M points).  asr_hip_shard_comm_rccl_create
-// therefore makes this stream first; processes that initialise RCCL before they create a context should raise
-// GPU_MAX_HW_QUEUES to 8 (bench.py does).
+// therefore makes this stream first; processes that initialise RCCL should create the context before the communicator.
 int asr_ctx_ensure_aux(asr_hip_context* ctx) {
     if (ctx->aux) return ASR_HIP_OK;
     ASR_HIP_CHECK(ctx, hipSetDevice(ctx->device));

@@ -1,5 +1,5 @@
 import os, sys
-REPO = "/root/repo"
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "adaptive-surface-reconstruction_amd")]
 import torch
 from asr_hip import synth

@@ -3,7 +3,6 @@ may be garbage): usage: ASR_EXP_LIB=path python scripts/exp_time.py"""
 import os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "adaptive-surface-reconstruction_amd")]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 from asr_hip import _lib
 if os.environ.get("ASR_EXP_LIB"):

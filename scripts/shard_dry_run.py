@@ -6,7 +6,6 @@ measurement.  usage: python scripts/shard_dry_run.py [n_points]"""
 import ctypes, os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "adaptive-surface-reconstruction_amd")]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 from asr_hip import _lib, synth
 from asr_hip.pipeline import ImplicitPipeline

@@ -1,5 +1,6 @@
 import os, sys, time
-sys.path[:0] = ["/root/repo", "/root/repo/adaptive-surface-reconstruction_amd"]
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "adaptive-surface-reconstruction_amd")]
 import torch
 from asr_hip import synth, sharding
 from asr_hip.sharding import ShardedImplicitPipeline
