@@ -373,7 +373,7 @@ int asr_hip_grid_neighbors_count(asr_hip_context* ctx, const uint64_t* keys, int
     if (v < 0 || !row_splits_out || !num_pairs || (v > 0 && !keys))
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "grid_neighbors_count: null argument");
     ctx->scratch.reset();
-    return asr_geom_neighbors_count(ctx, keys, v, row_splits_out, num_pairs);
+    return asr_geom_grid_neighbors_count(ctx, keys, v, nullptr, 0, row_splits_out, num_pairs);
 }
 int asr_hip_grid_neighbors_fill(asr_hip_context* ctx, const uint64_t* keys, int64_t v,
                                 const int64_t* row_splits, int32_t* index_out,
@@ -382,15 +382,20 @@ int asr_hip_grid_neighbors_fill(asr_hip_context* ctx, const uint64_t* keys, int6
     if (v < 0 || (v > 0 && (!keys || !row_splits || !index_out || !kernel_index_out)))
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "grid_neighbors_fill: null argument");
     ctx->scratch.reset();
-    return asr_geom_neighbors_fill(ctx, keys, v, row_splits, index_out, kernel_index_out);
+    return asr_geom_grid_neighbors_fill(ctx, keys, v, nullptr, 0, row_splits, index_out, kernel_index_out);
 }
 int asr_hip_grid_neighbors_rows_count(asr_hip_context* ctx, const uint64_t* keys, int64_t v, const int32_t* rows,
                                       int64_t num_rows, int64_t* row_splits_out, int64_t* num_pairs) {
     CTX_GUARD(ctx);
     if (v < 0 || num_rows < 0 || !row_splits_out || !num_pairs || (v > 0 && !keys) || (num_rows > 0 && !rows))
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "grid_neighbors_rows_count: null argument");
+    if (num_rows == 0) {  // no lists: row splits all zeros
+        *num_pairs = 0;
+        ASR_HIP_CHECK(ctx, hipMemsetAsync(row_splits_out, 0, (v + 1) * sizeof(int64_t), ctx->stream));
+        return ASR_HIP_OK;
+    }
     ctx->scratch.reset();
-    return asr_geom_neighbors_rows_count(ctx, keys, v, rows, num_rows, row_splits_out, num_pairs);
+    return asr_geom_grid_neighbors_count(ctx, keys, v, rows, num_rows, row_splits_out, num_pairs);
 }
 int asr_hip_grid_neighbors_rows_fill(asr_hip_context* ctx, const uint64_t* keys, int64_t v, const int32_t* rows,
                                      int64_t num_rows, const int64_t* row_splits, int32_t* index_out,
@@ -398,14 +403,16 @@ int asr_hip_grid_neighbors_rows_fill(asr_hip_context* ctx, const uint64_t* keys,
     CTX_GUARD(ctx);
     if (v < 0 || num_rows < 0 || (num_rows > 0 && (!keys || !rows || !row_splits || !index_out || !kernel_index_out)))
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "grid_neighbors_rows_fill: null argument");
+    if (num_rows == 0) return ASR_HIP_OK;
     ctx->scratch.reset();
-    return asr_geom_neighbors_rows_fill(ctx, keys, v, rows, num_rows, row_splits, index_out, kernel_index_out);
+    return asr_geom_grid_neighbors_fill(ctx, keys, v, rows, num_rows, row_splits, index_out, kernel_index_out);
 }
 int asr_hip_grid_coarsen_count(asr_hip_context* ctx, const uint64_t* keys, int64_t v,
                                int64_t* v_out) {
     CTX_GUARD(ctx);
     if (v < 0 || !v_out || (v > 0 && !keys))
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "grid_coarsen_count: null argument");
+    ctx->scratch.reset();
     return asr_geom_coarsen_count(ctx, keys, v, v_out);
 }
 int asr_hip_grid_coarsen_fill(asr_hip_context* ctx, const uint64_t* keys, int64_t v,
@@ -1084,10 +1091,8 @@ int build_coarse_grids(asr_hip_context* ctx) {
         g = GridDev();
         ctx->scratch.reset();
         GridDev& prev = ctx->grids[i - 1];
-        // (the keys of every grid are location codes of at most the deepest leaf's level: the sort skips the rest)
         ASR_TRY(asr_geom_coarsen_build(ctx, ctx->persist, prev.keys, prev.v, &g.keys, &g.v, &prev.up_idx,
-                                       &prev.up_kidx, &prev.up_rs, &prev.down_idx, &prev.down_kidx, &prev.down_rs,
-                                       ctx->leaf_lmax >= 0 ? 3 * ctx->leaf_lmax + 1 : 64));
+                                       &prev.up_kidx, &prev.up_rs, &prev.down_idx, &prev.down_kidx, &prev.down_rs));
         prev.perm_up = arena_alloc<int32_t>(ctx->persist, prev.v);
         prev.perm_down = arena_alloc<int32_t>(ctx->persist, g.v);
         if (!prev.perm_up || !prev.perm_down) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");

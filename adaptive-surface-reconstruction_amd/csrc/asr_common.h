@@ -385,15 +385,12 @@ int asr_geom_precells(asr_hip_context* ctx, Arena& keep);
 // Morton order of the points (+ radii) into ctx->pindex, arrays in `keep`
 int asr_geom_presort(asr_hip_context* ctx, Arena& keep, const asr_octree_frame* frame, const float* pts,
                      const float* radii, i64 n, float radius_scale = 0.f, int max_depth = 21);
-int asr_geom_neighbors_count(asr_hip_context* ctx, const u64* keys, i64 v, i64* rs, i64* num_pairs);
-int asr_geom_neighbors_fill(asr_hip_context* ctx, const u64* keys, i64 v, const i64* rs,
-                            int32_t* idx, uint8_t* kidx);
-int asr_geom_neighbors_rows_count(asr_hip_context* ctx, const u64* keys, i64 v, const int32_t* rows, i64 nrows, i64* rs,
+// the stand-alone neighbour lists of one grid (asr_hip_grid_neighbors_*); rows (optional, nrows entries): the lists of
+// those rows only, the other rows stay empty
+int asr_geom_grid_neighbors_count(asr_hip_context* ctx, const u64* keys, i64 v, const int32_t* rows, i64 nrows, i64* rs,
                                   i64* num_pairs);
-int asr_geom_neighbors_rows_fill(asr_hip_context* ctx, const u64* keys, i64 v, const int32_t* rows, i64 nrows,
+int asr_geom_grid_neighbors_fill(asr_hip_context* ctx, const u64* keys, i64 v, const int32_t* rows, i64 nrows,
                                  const i64* rs, int32_t* idx, uint8_t* kidx);
-int asr_geom_neighbors_build(asr_hip_context* ctx, Arena& out_arena, const u64* keys, i64 v,
-                             i64** rs_out, int32_t** idx_out, uint8_t** kidx_out, i64* num_pairs);
 // the neighbour lists of all grids of a hierarchy in ONE pass: one launch each for the key maps, the counting pass and
 // the filling pass, one scan, one read-back of the pair counts (round 4; was five times count / scan / read-back / fill)
 struct asr_nb_job {
@@ -418,13 +415,13 @@ struct asr_row_group_job {
 };
 int asr_geom_row_groups_batch(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, i64 seg);
 int asr_geom_coarsen_count(asr_hip_context* ctx, const u64* keys, i64 v, i64* v_out);
-// down_*: optional inverted up lists (rows = coarse voxels; what open3d::invert_neighbors_list returns for the up lists)
+// EINVAL when v_out is not what asr_geom_coarsen_count gives
 int asr_geom_coarsen_fill(asr_hip_context* ctx, const u64* keys, i64 v, u64* out_keys, i64 v_out,
-                          int32_t* up_idx, uint8_t* up_kidx, i64* up_rs, int32_t* down_idx = nullptr,
-                          uint8_t* down_kidx = nullptr, i64* down_rs = nullptr);
+                          int32_t* up_idx, uint8_t* up_kidx, i64* up_rs);
+// down_*: the inverted up lists (rows = coarse voxels; what open3d::invert_neighbors_list returns for the up lists)
 int asr_geom_coarsen_build(asr_hip_context* ctx, Arena& keep, const u64* keys, i64 v, u64** out_keys, i64* v_out,
                            int32_t** up_idx, uint8_t** up_kidx, i64** up_rs, int32_t** down_idx, uint8_t** down_kidx,
-                           i64** down_rs, int key_bits = 64);  // key_bits: significant bits of the largest key
+                           i64** down_rs);
 int asr_geom_voxel_info(asr_hip_context* ctx, const asr_octree_frame* frame, const u64* keys,
                         i64 v, float* centers, float* sizes);
 // keep: arena for the Morton-ordered point arrays (scratch when null); fill: spos (optional) receives

@@ -443,120 +443,14 @@ __device__ inline int neighbor_candidate(const HashTab& t, u64 key, int x, int y
     }
 }
 
-// The hits of the counting pass are parked (neighbour index + slot, NB_STAGE per row) so that the fill pass is a
-// copy for all but the few rows with more neighbours: the 8..13 hash probes per voxel are not repeated.
-constexpr int NB_STAGE = 16;
-__global__ void k_neighbors_count(const u64* keys, i64 v, HashTab t, i64* counts, u64* masks, int32_t* stage_idx,
-                                  uint8_t* stage_slot) {
-    i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    if (i > v) return;
-    if (i == v) {
-        counts[v] = 0;
-        return;
-    }
-    u64 key = keys[i];
-    int x, y, z, lev;
-    asr_key_coord(key, x, y, z, lev);
-    u64 m = 0;
-    int n = 1;
-#define ASR_NB_HIT(c_, idx_, slot_)                                   \
-    {                                                                 \
-        m |= u64(1) << (c_);                                          \
-        if (stage_idx && n - 1 < NB_STAGE) {                          \
-            stage_idx[i * NB_STAGE + (n - 1)] = (idx_);               \
-            stage_slot[i * NB_STAGE + (n - 1)] = (uint8_t)(slot_);    \
-        }                                                             \
-        ++n;                                                          \
-    }
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        int slot = 0;
-        const int idx = neighbor_candidate(t, key, x, y, z, lev, c, slot);
-        if (idx >= 0) ASR_NB_HIT(c, idx, slot)
-    }
-    // The voxels of a grid are disjoint cells: where the same-level neighbour across a face exists,
-    // neither its four children nor its parent can, so those five probes are skipped (36 -> ~13 probes
-    // per voxel on a scan; the resulting mask is the same).
-#pragma unroll 6
-    for (int c = 6; c < 36; ++c) {
-        const int face = c < 30 ? (c - 6) >> 2 : c - 30;
-        if ((m >> face) & 1) continue;
-        int slot = 0;
-        const int idx = neighbor_candidate(t, key, x, y, z, lev, c, slot);
-        if (idx >= 0) ASR_NB_HIT(c, idx, slot)
-    }
-#undef ASR_NB_HIT
-    counts[i] = n;
-    if (masks) masks[i] = m;
-}
-__global__ void k_neighbors_fill(const u64* keys, i64 v, HashTab t, const i64* rs, const u64* masks,
-                                 const int32_t* stage_idx, const uint8_t* stage_slot, int32_t* nidx, uint8_t* nkidx) {
-    i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    if (i >= v) return;
-    i64 o = rs[i];
-    const int n = (int)(rs[i + 1] - o);
-    nidx[o] = (int32_t)i;
-    nkidx[o] = 0;
-    ++o;
-    if (stage_idx && n - 1 <= NB_STAGE) {  // the candidate order of the counting pass is ascending slot order
-        for (int j = 0; j < n - 1; ++j) {
-            nidx[o + j] = stage_idx[i * NB_STAGE + j];
-            nkidx[o + j] = stage_slot[i * NB_STAGE + j];
-        }
-        return;
-    }
-    u64 key = keys[i];
-    int x, y, z, lev;
-    asr_key_coord(key, x, y, z, lev);
-    u64 m = masks ? masks[i] : ~u64(0);
-    for (int c = 0; c < 36; ++c) {
-        if (!((m >> c) & 1)) continue;
-        int slot;
-        int idx = neighbor_candidate(t, key, x, y, z, lev, c, slot);
-        if (idx >= 0) {
-            nidx[o] = idx;
-            nkidx[o] = (uint8_t)slot;
-            ++o;
-        }
-    }
-}
-
-// The same for a LIST of rows (a rank of the one-scan sharding builds the lists of the voxels it owns): counts of
-// the other rows stay 0, so the row splits keep their full length and the entries of the listed rows are compact.
-__device__ inline int neighbors_of_row(const u64* keys, i64 i, const HashTab& t, int32_t* nidx, uint8_t* nkidx) {
-    const u64 key = keys[i];
-    int x, y, z, lev;
-    asr_key_coord(key, x, y, z, lev);
-    u64 m = 0;
-    int n = 0;
-    if (nidx) {
-        nidx[0] = (int32_t)i;
-        nkidx[0] = 0;
-    }
-    ++n;
-    for (int c = 0; c < 36; ++c) {
-        if (c >= 6) {  // a same-level neighbour across a face rules out its children and its parent (see above)
-            const int face = c < 30 ? (c - 6) >> 2 : c - 30;
-            if ((m >> face) & 1) continue;
-        }
-        int slot = 0;
-        const int idx = neighbor_candidate(t, key, x, y, z, lev, c, slot);
-        if (idx < 0) continue;
-        m |= u64(1) << c;
-        if (nidx) {
-            nidx[n] = idx;
-            nkidx[n] = (uint8_t)slot;
-        }
-        ++n;
-    }
-    return n;
-}
-// public row lists / key lists are caller data: a bad entry must become an error, not an out-of-bounds write
-__global__ void k_check_rows(const int32_t* rows, i64 nrows, i64 v, int* cnt) {
+// public row lists / key lists are caller data: a bad entry must become an error, not an out-of-bounds write.
+// mark (optional, zeroed int32[v]): 1 at the listed rows, the row filter of a neighbour batch
+__global__ void k_check_rows(const int32_t* rows, i64 nrows, i64 v, int* cnt, int32_t* mark) {
     const i64 r = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     if (r >= nrows) return;
     const i64 q = rows[r];
     if (q < 0 || q >= v || (r > 0 && rows[r - 1] >= q)) cnt[3] = 1;  // in range, strictly ascending
+    else if (mark) mark[q] = 1;
 }
 __global__ void k_check_keys(const u64* keys, i64 n, int* cnt) {
     const i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x;
@@ -565,27 +459,15 @@ __global__ void k_check_keys(const u64* keys, i64 n, int* cnt) {
     // a location code: leading bit at position 3 * level, level <= ASR_MAX_LEVEL (0 is the tables' empty sentinel)
     if (k == 0 || (63 - __clzll((long long)k)) % 3 != 0) cnt[3] = 1;
 }
-__global__ void k_neighbors_count_rows(const u64* keys, HashTab t, const int32_t* rows, i64 nrows, i64* counts) {
-    const i64 r = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    if (r >= nrows) return;
-    const i64 i = rows[r];
-    counts[i] = neighbors_of_row(keys, i, t, nullptr, nullptr);
-}
-__global__ void k_neighbors_fill_rows(const u64* keys, HashTab t, const int32_t* rows, i64 nrows, const i64* rs,
-                                      int32_t* nidx, uint8_t* nkidx) {
-    const i64 r = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    if (r >= nrows) return;
-    const i64 i = rows[r];
-    const i64 o = rs[i];
-    (void)neighbors_of_row(keys, i, t, nidx + o, nkidx + o);
-}
 
-// ------------------------------------------------------------------------------------------
-// The same for ALL grids of a hierarchy in one launch each (asr_geom_neighbors_build_batch): the coarse grids hold a few
-// thousand voxels, whose 13-odd dependent probes cost a level-0 kernel's latency each when launched one by one.  Rows of
-// all jobs share one index space, every job followed by one terminator entry, so that ONE exclusive scan gives every
-// job's row splits (shifted by the job's first value) and the pair counts at the job boundaries.
-// ------------------------------------------------------------------------------------------
+// The lists of ALL grids of a hierarchy in one launch each (asr_geom_neighbors_build_batch; the stand-alone operators
+// are a batch of one grid): the coarse grids hold a few thousand voxels, whose 13-odd dependent probes cost a level-0
+// kernel's latency each when launched one by one.  Rows of all jobs share one index space, every job followed by one
+// terminator entry, so that ONE exclusive scan gives every job's row splits (shifted by the job's first value) and the
+// pair counts at the job boundaries.
+// The hits of the counting pass are parked (neighbour index + slot, NB_STAGE per row) so that the fill pass is a copy for
+// all but the few rows with more neighbours: the 8..13 hash probes per voxel are not repeated.
+constexpr int NB_STAGE = 16;
 constexpr int NB_MAX_JOBS = 8;
 struct NbBatch {
     int n;
@@ -593,7 +475,7 @@ struct NbBatch {
     i64 v[NB_MAX_JOBS];
     const u64* keys[NB_MAX_JOBS];
     HashTab tab[NB_MAX_JOBS];
-    i64* rs[NB_MAX_JOBS];
+    i64* rs[NB_MAX_JOBS];  // optional: the fill writes each job's row splits here
     int32_t* idx[NB_MAX_JOBS];
     uint8_t* kidx[NB_MAX_JOBS];
     const int32_t* owner[NB_MAX_JOBS];  // optional row filter (one rank of a sharded cloud builds its own rows)
@@ -616,6 +498,7 @@ __global__ void k_map_build_batch(NbBatch b, int* cnt) {
     else
         b.tab[j].vals[slot] = (int32_t)i;
 }
+// masks, stage_idx / stage_slot: optional, for the fill pass
 __global__ void k_neighbors_count_batch(NbBatch b, i64* counts, u64* masks, int32_t* stage_idx, uint8_t* stage_slot) {
     const i64 e = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     if (e >= b.base[b.n]) return;
@@ -627,7 +510,7 @@ __global__ void k_neighbors_count_batch(NbBatch b, i64* counts, u64* masks, int3
     }
     if (b.owner[j] && b.owner[j][i] != b.me[j]) {
         counts[e] = 0;
-        masks[e] = 0;
+        if (masks) masks[e] = 0;
         return;
     }
     const HashTab t = b.tab[j];
@@ -636,9 +519,12 @@ __global__ void k_neighbors_count_batch(NbBatch b, i64* counts, u64* masks, int3
     asr_key_coord(key, x, y, z, lev);
     u64 m = 0;
     int n = 1;
+    // The voxels of a grid are disjoint cells: where the same-level neighbour across a face exists, neither its four
+    // children nor its parent can, so those five probes are skipped (36 -> ~13 probes per voxel on a scan; the resulting
+    // mask is the same).
 #pragma unroll 6
     for (int c = 0; c < 36; ++c) {
-        if (c >= 6) {  // a same-level neighbour across a face rules out its children and its parent (k_neighbors_count)
+        if (c >= 6) {
             const int face = c < 30 ? (c - 6) >> 2 : c - 30;
             if ((m >> face) & 1) continue;
         }
@@ -646,20 +532,21 @@ __global__ void k_neighbors_count_batch(NbBatch b, i64* counts, u64* masks, int3
         const int idx = neighbor_candidate(t, key, x, y, z, lev, c, slot);
         if (idx < 0) continue;
         m |= u64(1) << c;
-        if (n - 1 < NB_STAGE) {
+        if (stage_idx && n - 1 < NB_STAGE) {
             stage_idx[e * NB_STAGE + (n - 1)] = idx;
             stage_slot[e * NB_STAGE + (n - 1)] = (uint8_t)slot;
         }
         ++n;
     }
     counts[e] = n;
-    masks[e] = m;
+    if (masks) masks[e] = m;
 }
 // totals[j] = pairs of job j (scan value at the next job's first entry minus the job's own)
 __global__ void k_nb_totals(NbBatch b, const i64* scan, i64* totals) {
     const int j = threadIdx.x;
     if (j < b.n) totals[j] = scan[b.base[j] + b.v[j]] - scan[b.base[j]];
 }
+// without masks and staging every row probes all 36 candidates
 __global__ void k_neighbors_fill_batch(NbBatch b, const i64* scan, const u64* masks, const int32_t* stage_idx,
                                        const uint8_t* stage_slot) {
     const i64 e = blockIdx.x * (i64)blockDim.x + threadIdx.x;
@@ -668,7 +555,7 @@ __global__ void k_neighbors_fill_batch(NbBatch b, const i64* scan, const u64* ma
     const i64 i = e - b.base[j];
     const i64 first = scan[b.base[j]];
     i64 o = scan[e] - first;
-    b.rs[j][i] = o;  // (the terminator writes rs[v] = pairs of the job)
+    if (b.rs[j]) b.rs[j][i] = o;  // (the terminator writes rs[v] = pairs of the job)
     if (i >= b.v[j]) return;
     const int n = (int)(scan[e + 1] - first - o);
     if (n == 0) return;  // a row of another rank
@@ -677,7 +564,7 @@ __global__ void k_neighbors_fill_batch(NbBatch b, const i64* scan, const u64* ma
     nidx[o] = (int32_t)i;
     nkidx[o] = 0;
     ++o;
-    if (n - 1 <= NB_STAGE) {  // the candidate order of the counting pass is ascending slot order
+    if (stage_idx && n - 1 <= NB_STAGE) {  // the candidate order of the counting pass is ascending slot order
         for (int q = 0; q < n - 1; ++q) {
             nidx[o + q] = stage_idx[e * NB_STAGE + q];
             nkidx[o + q] = stage_slot[e * NB_STAGE + q];
@@ -688,7 +575,7 @@ __global__ void k_neighbors_fill_batch(NbBatch b, const i64* scan, const u64* ma
     const u64 key = b.keys[j][i];
     int x, y, z, lev;
     asr_key_coord(key, x, y, z, lev);
-    const u64 m = masks[e];
+    const u64 m = masks ? masks[e] : ~u64(0);
     for (int c = 0; c < 36; ++c) {
         if (!((m >> c) & 1)) continue;
         int slot;
@@ -715,19 +602,6 @@ __device__ inline int coarsen_state(const u64* keys, i64 v, i64 i) {
     i64 h = i - (i64)(k & 7);
     if (h >= 0 && keys[h] == (k & ~u64(7)) && merged_head(keys, v, h)) return 2;
     return 0;
-}
-__global__ void k_coarsen_count(const u64* keys, i64 v, int* cnt) {
-    i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    bool keep = i < v && coarsen_state(keys, v, i) != 2;
-    (void)block_append(keep, &cnt[5]);
-}
-__global__ void k_coarsen_emit(const u64* keys, i64 v, u64* out_keys, int32_t* out_src, int* cnt) {
-    i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    int st = i < v ? coarsen_state(keys, v, i) : 2;
-    int pos = block_append(st != 2, &cnt[5]);
-    if (st == 2) return;
-    out_keys[pos] = st == 1 ? keys[i] >> 3 : keys[i];
-    out_src[pos] = (int32_t)i;
 }
 // CombineSiblings without a sort (round 4).  The coarse key set is the kept keys plus one parent per merged group; both
 // sub-sequences are already sorted in input order, and location codes sort level-major, so an emitted key's position in
@@ -2348,34 +2222,59 @@ int asr_geom_octree_build(asr_hip_context* ctx, const asr_octree_frame* frame, c
     ASR_FAIL(ctx, ASR_HIP_ELOGIC, "octree hash table overflow after 6 growth attempts");
 }
 
-static int build_key_map(asr_hip_context* ctx, const u64* keys, i64 v, HashTab& t, int grow = 0) {
+// Key maps of all jobs of `b` (one allocation and one memset for all tables, one launch), then `pass` -- the work that
+// uses them, enqueued on ctx->stream -- and ONE read-back of the overflow flag.  A map that lost keys (see TabProbe:
+// lattice-like key sets fill "their" positions of the 64-slot buckets early) is rebuilt four times the size and `pass`
+// run again, so that every caller either sees all keys or fails; none drops neighbours silently.
+template <class Pass>
+static int nb_key_maps(asr_hip_context* ctx, NbBatch& b, Pass&& pass) {
     ASR_TRY(ensure_flags(ctx));
-    u64 cap = next_pow2((u64)std::max<i64>(1024, 2 * v)) << grow;
-    ASR_TRY(make_table(ctx, ctx->scratch, cap, true, t));
-    ASR_TRY(fresh_flags(ctx));
-    k_map_build<<<grid_for(v, BLK), BLK, 0, ctx->stream>>>(keys, v, t, ctx->d_flags);
-    ASR_CHECK_LAUNCH(ctx);
-    return ASR_HIP_OK;
-}
-
-// The same for the stand-alone operators: the overflow flag is read back (one synchronisation) and a map that lost keys
-// -- lattice-like key sets fill "their" positions of the 64-slot buckets early -- is rebuilt four times the size, so that
-// every entry point either sees all keys or fails; none drops neighbours silently.
-static int build_key_map_complete(asr_hip_context* ctx, const u64* keys, i64 v, HashTab& t) {
     for (int grow = 0;; grow += 2) {
-        ASR_TRY(build_key_map(ctx, keys, v, t, grow));
+        u64 caps[NB_MAX_JOBS], cap_sum = 0;
+        for (int j = 0; j < b.n; ++j) {
+            caps[j] = next_pow2((u64)std::max<i64>(1024, 2 * b.v[j])) << grow;
+            cap_sum += caps[j];
+        }
+        u64* tkeys = arena_alloc<u64>(ctx->scratch, cap_sum);
+        int32_t* tvals = arena_alloc<int32_t>(ctx->scratch, cap_sum);
+        if (!tkeys || !tvals) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+        u64 off = 0;
+        for (int j = 0; j < b.n; ++j) {
+            b.tab[j] = HashTab{tkeys + off, tvals + off, caps[j] - 1};
+            off += caps[j];
+        }
+        ASR_HIP_CHECK(ctx, hipMemsetAsync(tkeys, 0, cap_sum * sizeof(u64), ctx->stream));
+        ASR_TRY(fresh_flags(ctx));
+        k_map_build_batch<<<grid_for(b.base[b.n], BLK), BLK, 0, ctx->stream>>>(b, ctx->d_flags);
+        ASR_CHECK_LAUNCH(ctx);
+        ASR_TRY(pass());
         int host[16];
-        ASR_HIP_CHECK(ctx, hipMemcpyAsync(host, ctx->d_flags, 16 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        ASR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        ASR_TRY(read_flags(ctx, host));
         if (!host[1]) return ASR_HIP_OK;
         if (grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "voxel key map overflow");
     }
 }
 
-static int check_row_list(asr_hip_context* ctx, const int32_t* rows, i64 nrows, i64 v) {
+// the stand-alone operators: one grid, a batch of one job whose row splits and lists are the caller's
+static NbBatch nb_one_grid(const u64* keys, i64 v) {
+    NbBatch b;
+    b.n = 1;
+    b.base[0] = 0;
+    b.base[1] = v + 1;
+    b.v[0] = v;
+    b.keys[0] = keys;
+    b.rs[0] = nullptr;
+    b.idx[0] = nullptr;
+    b.kidx[0] = nullptr;
+    b.owner[0] = nullptr;
+    b.me[0] = 1;
+    return b;
+}
+
+static int check_row_list(asr_hip_context* ctx, const int32_t* rows, i64 nrows, i64 v, int32_t* mark = nullptr) {
     ASR_TRY(ensure_flags(ctx));
     ASR_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags + 3, 0, sizeof(int), ctx->stream));
-    k_check_rows<<<grid_for(nrows, BLK), BLK, 0, ctx->stream>>>(rows, nrows, v, ctx->d_flags);
+    k_check_rows<<<grid_for(nrows, BLK), BLK, 0, ctx->stream>>>(rows, nrows, v, ctx->d_flags, mark);
     ASR_CHECK_LAUNCH(ctx);
     int host[16];
     ASR_TRY(read_flags(ctx, host));
@@ -2383,100 +2282,46 @@ static int check_row_list(asr_hip_context* ctx, const int32_t* rows, i64 nrows, 
     return ASR_HIP_OK;
 }
 
-int asr_geom_neighbors_count(asr_hip_context* ctx, const u64* keys, i64 v, i64* rs, i64* num_pairs) {
-    if (v <= 0) {
-        *num_pairs = 0;
-        if (rs) ASR_HIP_CHECK(ctx, hipMemsetAsync(rs, 0, sizeof(i64), ctx->stream));
-        return ASR_HIP_OK;
-    }
-    HashTab t;
-    ASR_TRY(build_key_map_complete(ctx, keys, v, t));
-    i64* counts = arena_alloc<i64>(ctx->scratch, v + 1);
-    if (!counts) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-    k_neighbors_count<<<grid_for(v + 1, BLK), BLK, 0, ctx->stream>>>(keys, v, t, counts, nullptr, nullptr, nullptr);
-    ASR_CHECK_LAUNCH(ctx);
-    ASR_TRY(scan_counts(ctx, ctx->scratch, counts, rs, v + 1));
-    ASR_TRY(read_i64(ctx, rs + v, num_pairs));
-    return ASR_HIP_OK;
-}
-int asr_geom_neighbors_fill(asr_hip_context* ctx, const u64* keys, i64 v, const i64* rs,
-                            int32_t* idx, uint8_t* kidx) {
-    if (v <= 0) return ASR_HIP_OK;
-    HashTab t;
-    ASR_TRY(build_key_map_complete(ctx, keys, v, t));
-    k_neighbors_fill<<<grid_for(v, BLK), BLK, 0, ctx->stream>>>(keys, v, t, rs, nullptr, nullptr, nullptr, idx, kidx);
-    ASR_CHECK_LAUNCH(ctx);
-    return ASR_HIP_OK;
-}
-int asr_geom_neighbors_rows_count(asr_hip_context* ctx, const u64* keys, i64 v, const int32_t* rows, i64 nrows, i64* rs,
+int asr_geom_grid_neighbors_count(asr_hip_context* ctx, const u64* keys, i64 v, const int32_t* rows, i64 nrows, i64* rs,
                                   i64* num_pairs) {
     *num_pairs = 0;
     if (v <= 0) {
-        if (rs) ASR_HIP_CHECK(ctx, hipMemsetAsync(rs, 0, sizeof(i64), ctx->stream));
+        ASR_HIP_CHECK(ctx, hipMemsetAsync(rs, 0, sizeof(i64), ctx->stream));
         return ASR_HIP_OK;
     }
-    HashTab t;
-    ASR_TRY(build_key_map_complete(ctx, keys, v, t));
+    NbBatch b = nb_one_grid(keys, v);
+    if (rows) {  // the row list becomes the batch's row filter: 1 at the listed rows
+        int32_t* mark = arena_alloc<int32_t>(ctx->scratch, v);
+        if (!mark) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+        ASR_HIP_CHECK(ctx, hipMemsetAsync(mark, 0, v * sizeof(int32_t), ctx->stream));
+        ASR_TRY(check_row_list(ctx, rows, nrows, v, mark));
+        b.owner[0] = mark;
+    }
     i64* counts = arena_alloc<i64>(ctx->scratch, v + 1);
     if (!counts) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-    ASR_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, (v + 1) * sizeof(i64), ctx->stream));
-    if (nrows > 0) {
-        ASR_TRY(check_row_list(ctx, rows, nrows, v));
-        k_neighbors_count_rows<<<grid_for(nrows, BLK), BLK, 0, ctx->stream>>>(keys, t, rows, nrows, counts);
+    ASR_TRY(nb_key_maps(ctx, b, [&]() -> int {
+        k_neighbors_count_batch<<<grid_for(v + 1, BLK), BLK, 0, ctx->stream>>>(b, counts, nullptr, nullptr, nullptr);
         ASR_CHECK_LAUNCH(ctx);
-    }
-    ASR_TRY(scan_counts(ctx, ctx->scratch, counts, rs, v + 1));
-    ASR_TRY(read_i64(ctx, rs + v, num_pairs));
-    return ASR_HIP_OK;
+        return scan_counts(ctx, ctx->scratch, counts, rs, v + 1);
+    }));
+    return read_i64(ctx, rs + v, num_pairs);
 }
-int asr_geom_neighbors_rows_fill(asr_hip_context* ctx, const u64* keys, i64 v, const int32_t* rows, i64 nrows,
+// rows: checked only; the rows that are not listed have no entries in rs and are skipped
+int asr_geom_grid_neighbors_fill(asr_hip_context* ctx, const u64* keys, i64 v, const int32_t* rows, i64 nrows,
                                  const i64* rs, int32_t* idx, uint8_t* kidx) {
-    if (v <= 0 || nrows <= 0) return ASR_HIP_OK;
-    HashTab t;
-    ASR_TRY(build_key_map_complete(ctx, keys, v, t));
-    ASR_TRY(check_row_list(ctx, rows, nrows, v));
-    k_neighbors_fill_rows<<<grid_for(nrows, BLK), BLK, 0, ctx->stream>>>(keys, t, rows, nrows, rs, idx, kidx);
+    if (v <= 0) return ASR_HIP_OK;
+    if (rows) ASR_TRY(check_row_list(ctx, rows, nrows, v));
+    NbBatch b = nb_one_grid(keys, v);
+    b.idx[0] = idx;
+    b.kidx[0] = kidx;
+    ASR_TRY(nb_key_maps(ctx, b, [] { return ASR_HIP_OK; }));
+    k_neighbors_fill_batch<<<grid_for(v + 1, BLK), BLK, 0, ctx->stream>>>(b, rs, nullptr, nullptr, nullptr);
     ASR_CHECK_LAUNCH(ctx);
     return ASR_HIP_OK;
-}
-// fused variant for the whole-path driver: one map build, masks carried from count to fill.
-int asr_geom_neighbors_build(asr_hip_context* ctx, Arena& out_arena, const u64* keys, i64 v,
-                             i64** rs_out, int32_t** idx_out, uint8_t** kidx_out, i64* num_pairs) {
-    i64* rs = arena_alloc<i64>(out_arena, v + 1);
-    if (!rs) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-    for (int grow = 0;; grow += 2) {  // a key map that overflowed (see TabProbe) is rebuilt four times the size
-        HashTab t;
-        ASR_TRY(build_key_map(ctx, keys, v, t, grow));
-        i64* counts = arena_alloc<i64>(ctx->scratch, v + 1);
-        u64* masks = arena_alloc<u64>(ctx->scratch, v);
-        int32_t* st_idx = arena_alloc<int32_t>(ctx->scratch, (size_t)v * NB_STAGE);
-        uint8_t* st_slot = arena_alloc<uint8_t>(ctx->scratch, (size_t)v * NB_STAGE);
-        if (!counts || !masks || !st_idx || !st_slot) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-        k_neighbors_count<<<grid_for(v + 1, BLK), BLK, 0, ctx->stream>>>(keys, v, t, counts, masks, st_idx, st_slot);
-        ASR_CHECK_LAUNCH(ctx);
-        ASR_TRY(scan_counts(ctx, ctx->scratch, counts, rs, v + 1));
-        int host[16];
-        ASR_HIP_CHECK(ctx, hipMemcpyAsync(host, ctx->d_flags, 16 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        ASR_TRY(read_i64(ctx, rs + v, num_pairs));  // synchronises: the flags have arrived as well
-        if (host[1]) {
-            if (grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "voxel key map overflow");
-            continue;
-        }
-        int32_t* idx = arena_alloc<int32_t>(out_arena, *num_pairs);
-        uint8_t* kidx = arena_alloc<uint8_t>(out_arena, *num_pairs);
-        if (!idx || !kidx) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-        k_neighbors_fill<<<grid_for(v, BLK), BLK, 0, ctx->stream>>>(keys, v, t, rs, masks, st_idx, st_slot, idx, kidx);
-        ASR_CHECK_LAUNCH(ctx);
-        *rs_out = rs;
-        *idx_out = idx;
-        *kidx_out = kidx;
-        return ASR_HIP_OK;
-    }
 }
 
 int asr_geom_neighbors_build_batch(asr_hip_context* ctx, Arena& out_arena, asr_nb_job* jobs, int n) {
     if (n < 1 || n > NB_MAX_JOBS) ASR_FAIL(ctx, ASR_HIP_EINVAL, "neighbors_build_batch: 1..%d jobs", NB_MAX_JOBS);
-    ASR_TRY(ensure_flags(ctx));
     NbBatch b;
     b.n = n;
     i64 total = 0;
@@ -2495,58 +2340,41 @@ int asr_geom_neighbors_build_batch(asr_hip_context* ctx, Arena& out_arena, asr_n
         b.me[j] = jobs[j].me;
     }
     b.base[n] = total;
-    for (int grow = 0;; grow += 2) {  // key maps that overflowed (see TabProbe) are rebuilt four times the size
-        u64 caps[NB_MAX_JOBS], cap_sum = 0;
-        for (int j = 0; j < n; ++j) {
-            caps[j] = next_pow2((u64)std::max<i64>(1024, 2 * jobs[j].v)) << grow;
-            cap_sum += caps[j];
-        }
-        u64* tkeys = arena_alloc<u64>(ctx->scratch, cap_sum);  // one allocation, one memset for all tables
-        int32_t* tvals = arena_alloc<int32_t>(ctx->scratch, cap_sum);
+    i64* scan = nullptr;
+    u64* masks = nullptr;
+    int32_t* st_idx = nullptr;
+    uint8_t* st_slot = nullptr;
+    i64 host_totals[NB_MAX_JOBS];
+    ASR_TRY(nb_key_maps(ctx, b, [&]() -> int {
         i64* counts = arena_alloc<i64>(ctx->scratch, total + 1);
-        i64* scan = arena_alloc<i64>(ctx->scratch, total + 1);
-        u64* masks = arena_alloc<u64>(ctx->scratch, total);
-        int32_t* st_idx = arena_alloc<int32_t>(ctx->scratch, (size_t)total * NB_STAGE);
-        uint8_t* st_slot = arena_alloc<uint8_t>(ctx->scratch, (size_t)total * NB_STAGE);
+        scan = arena_alloc<i64>(ctx->scratch, total + 1);
+        masks = arena_alloc<u64>(ctx->scratch, total);
+        st_idx = arena_alloc<int32_t>(ctx->scratch, (size_t)total * NB_STAGE);
+        st_slot = arena_alloc<uint8_t>(ctx->scratch, (size_t)total * NB_STAGE);
         i64* totals = arena_alloc<i64>(ctx->scratch, NB_MAX_JOBS);
-        if (!tkeys || !tvals || !counts || !scan || !masks || !st_idx || !st_slot || !totals)
+        if (!counts || !scan || !masks || !st_idx || !st_slot || !totals)
             ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-        u64 off = 0;
-        for (int j = 0; j < n; ++j) {
-            b.tab[j] = HashTab{tkeys + off, tvals + off, caps[j] - 1};
-            off += caps[j];
-        }
-        ASR_HIP_CHECK(ctx, hipMemsetAsync(tkeys, 0, cap_sum * sizeof(u64), ctx->stream));
-        ASR_TRY(fresh_flags(ctx));
         ASR_HIP_CHECK(ctx, hipMemsetAsync(counts + total, 0, sizeof(i64), ctx->stream));
-        k_map_build_batch<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, ctx->d_flags);
-        ASR_CHECK_LAUNCH(ctx);
         k_neighbors_count_batch<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, counts, masks, st_idx, st_slot);
         ASR_CHECK_LAUNCH(ctx);
         ASR_TRY(scan_counts(ctx, ctx->scratch, counts, scan, total + 1));
         k_nb_totals<<<1, 64, 0, ctx->stream>>>(b, scan, totals);
         ASR_CHECK_LAUNCH(ctx);
-        int host_flags[16];
-        i64 host_totals[NB_MAX_JOBS];
-        ASR_HIP_CHECK(ctx, hipMemcpyAsync(host_flags, ctx->d_flags, 16 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        // arrives with the read-back of the overflow flag
         ASR_HIP_CHECK(ctx, hipMemcpyAsync(host_totals, totals, n * sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-        ASR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (host_flags[1]) {
-            if (grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "voxel key map overflow");
-            continue;
-        }
-        for (int j = 0; j < n; ++j) {
-            jobs[j].p = host_totals[j];
-            jobs[j].idx = arena_alloc<int32_t>(out_arena, jobs[j].p);
-            jobs[j].kidx = arena_alloc<uint8_t>(out_arena, jobs[j].p);
-            if (!jobs[j].idx || !jobs[j].kidx) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-            b.idx[j] = jobs[j].idx;
-            b.kidx[j] = jobs[j].kidx;
-        }
-        k_neighbors_fill_batch<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, scan, masks, st_idx, st_slot);
-        ASR_CHECK_LAUNCH(ctx);
         return ASR_HIP_OK;
+    }));
+    for (int j = 0; j < n; ++j) {
+        jobs[j].p = host_totals[j];
+        jobs[j].idx = arena_alloc<int32_t>(out_arena, jobs[j].p);
+        jobs[j].kidx = arena_alloc<uint8_t>(out_arena, jobs[j].p);
+        if (!jobs[j].idx || !jobs[j].kidx) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+        b.idx[j] = jobs[j].idx;
+        b.kidx[j] = jobs[j].kidx;
     }
+    k_neighbors_fill_batch<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, scan, masks, st_idx, st_slot);
+    ASR_CHECK_LAUNCH(ctx);
+    return ASR_HIP_OK;
 }
 
 int asr_geom_row_groups(asr_hip_context* ctx, const uint8_t* kidx, const i64* rs, i64 v, i64 seg,
@@ -2736,80 +2564,80 @@ static int rg_batch_run(asr_hip_context* ctx, const asr_row_group_job* jobs, int
     return ASR_HIP_OK;
 }
 
-int asr_geom_coarsen_count(asr_hip_context* ctx, const u64* keys, i64 v, i64* v_out) {
-    ASR_TRY(ensure_flags(ctx));
-    if (v <= 0) {
-        *v_out = 0;
-        return ASR_HIP_OK;
-    }
-    int host[16];
-    ASR_TRY(fresh_flags(ctx));
-    k_coarsen_count<<<grid_for(v, BLK), BLK, 0, ctx->stream>>>(keys, v, ctx->d_flags);
+// CombineSiblings in two steps (k_coarsen_flags above); the keys are sorted and unique, as those of every grid.
+// Step 1: flags -> exclusive scan of the packed counts (kept | heads << 32; both below 2^31) -> one read-back of the
+// totals.  *pre (v + 2 entries, scratch) feeds step 2, *v_out = coarse voxels.
+static int coarsen_scan(asr_hip_context* ctx, const u64* keys, i64 v, u64** pre, i64* v_out) {
+    u64* packed = arena_alloc<u64>(ctx->scratch, v + 1);
+    *pre = arena_alloc<u64>(ctx->scratch, v + 2);
+    if (!packed || !*pre) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    k_coarsen_flags<<<grid_for(v + 1, BLK), BLK, 0, ctx->stream>>>(keys, v, packed);
     ASR_CHECK_LAUNCH(ctx);
-    ASR_TRY(read_flags(ctx, host));
-    *v_out = host[5];
+    size_t tb = 0;
+    ASR_HIP_CHECK(ctx, rocprim::exclusive_scan(nullptr, tb, packed, *pre, u64(0), (size_t)(v + 1), rocprim::plus<u64>(),
+                                               ctx->stream));
+    void* tmp = ctx->scratch.alloc(tb ? tb : 256);
+    if (!tmp) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    ASR_HIP_CHECK(ctx, rocprim::exclusive_scan(tmp, tb, packed, *pre, u64(0), (size_t)(v + 1), rocprim::plus<u64>(),
+                                               ctx->stream));
+    u64 totals = 0;
+    ASR_HIP_CHECK(ctx, hipMemcpyAsync(&totals, *pre + v, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    ASR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    *v_out = (i64)(totals & 0xffffffffu) + (i64)(totals >> 32);
     return ASR_HIP_OK;
 }
-int asr_geom_coarsen_fill(asr_hip_context* ctx, const u64* keys, i64 v, u64* out_keys, i64 v_out,
-                          int32_t* up_idx, uint8_t* up_kidx, i64* up_rs, int32_t* down_idx, uint8_t* down_kidx,
-                          i64* down_rs) {
-    ASR_TRY(ensure_flags(ctx));
-    if (v <= 0) return ASR_HIP_OK;
-    u64* k_u = arena_alloc<u64>(ctx->scratch, v_out);
-    int32_t* s_u = arena_alloc<int32_t>(ctx->scratch, v_out);
-    int32_t* s_s = arena_alloc<int32_t>(ctx->scratch, v_out);
-    if (!k_u || !s_u || !s_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-    ASR_TRY(fresh_flags(ctx));
-    k_coarsen_emit<<<grid_for(v, BLK), BLK, 0, ctx->stream>>>(keys, v, k_u, s_u, ctx->d_flags);
+// Step 2: the coarse keys, the up lists and, when down_rs is given, the down lists.  src: scratch int32[vo], the fine
+// index of every coarse voxel.
+static int coarsen_lists(asr_hip_context* ctx, const u64* keys, i64 v, const u64* pre, i64 vo, int32_t* src,
+                         u64* out_keys, int32_t* up_idx, uint8_t* up_kidx, i64* up_rs, int32_t* down_idx,
+                         uint8_t* down_kidx, i64* down_rs) {
+    k_coarsen_place<<<grid_for(v, BLK), BLK, 0, ctx->stream>>>(keys, v, pre, out_keys, src);
     ASR_CHECK_LAUNCH(ctx);
-    ASR_TRY((sort_pairs<u64, int32_t>(ctx, ctx->scratch, k_u, out_keys, s_u, s_s, v_out, 64)));
-    k_coarsen_up<<<grid_for(v_out, BLK), BLK, 0, ctx->stream>>>(keys, v, s_s, v_out, up_idx, up_kidx);
+    k_coarsen_up<<<grid_for(vo, BLK), BLK, 0, ctx->stream>>>(keys, v, src, vo, up_idx, up_kidx);
     ASR_CHECK_LAUNCH(ctx);
     k_iota64<<<grid_for(v + 1, BLK), BLK, 0, ctx->stream>>>(up_rs, v + 1);
     ASR_CHECK_LAUNCH(ctx);
-    if (down_rs) {  // the inverted lists, rows = coarse voxels
-        i64* cnt = arena_alloc<i64>(ctx->scratch, v_out + 1);
-        if (!cnt) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-        k_coarsen_down_count<<<grid_for(v_out + 1, BLK), BLK, 0, ctx->stream>>>(keys, v, s_s, v_out, cnt);
-        ASR_CHECK_LAUNCH(ctx);
-        ASR_TRY(scan_counts(ctx, ctx->scratch, cnt, down_rs, v_out + 1));
-        k_coarsen_down_fill<<<grid_for(v_out, BLK), BLK, 0, ctx->stream>>>(keys, v, s_s, v_out, down_rs, down_idx,
-                                                                          down_kidx);
-        ASR_CHECK_LAUNCH(ctx);
-    }
+    if (!down_rs) return ASR_HIP_OK;
+    i64* cnt = arena_alloc<i64>(ctx->scratch, vo + 1);
+    if (!cnt) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    k_coarsen_down_count<<<grid_for(vo + 1, BLK), BLK, 0, ctx->stream>>>(keys, v, src, vo, cnt);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(scan_counts(ctx, ctx->scratch, cnt, down_rs, vo + 1));
+    k_coarsen_down_fill<<<grid_for(vo, BLK), BLK, 0, ctx->stream>>>(keys, v, src, vo, down_rs, down_idx, down_kidx);
+    ASR_CHECK_LAUNCH(ctx);
     return ASR_HIP_OK;
 }
 
-// Whole-path variant: ONE pass over the fine keys (the emit kernel counts while it appends: no separate counting
-// kernel), one size read-back, outputs allocated from `keep`.
-int asr_geom_coarsen_build(asr_hip_context* ctx, Arena& keep, const u64* keys, i64 v, u64** out_keys, i64* v_out,
-                           int32_t** up_idx, uint8_t** up_kidx, i64** up_rs, int32_t** down_idx, uint8_t** down_kidx,
-                           i64** down_rs, int key_bits) {
-    ASR_TRY(ensure_flags(ctx));
+int asr_geom_coarsen_count(asr_hip_context* ctx, const u64* keys, i64 v, i64* v_out) {
     *v_out = 0;
     if (v <= 0) return ASR_HIP_OK;
-    (void)key_bits;
-    // flags -> exclusive scan of the packed counts (kept | heads << 32; both below 2^31) -> one read-back of the totals
-    u64* packed = arena_alloc<u64>(ctx->scratch, v + 1);
-    u64* pre = arena_alloc<u64>(ctx->scratch, v + 2);
-    int32_t* s_s = arena_alloc<int32_t>(ctx->scratch, v);
-    if (!packed || !pre || !s_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-    k_coarsen_flags<<<grid_for(v + 1, BLK), BLK, 0, ctx->stream>>>(keys, v, packed);
-    ASR_CHECK_LAUNCH(ctx);
-    {
-        size_t tb = 0;
-        ASR_HIP_CHECK(ctx, rocprim::exclusive_scan(nullptr, tb, packed, pre, u64(0), (size_t)(v + 1), rocprim::plus<u64>(),
-                                                   ctx->stream));
-        void* tmp = ctx->scratch.alloc(tb ? tb : 256);
-        if (!tmp) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-        ASR_HIP_CHECK(ctx, rocprim::exclusive_scan(tmp, tb, packed, pre, u64(0), (size_t)(v + 1), rocprim::plus<u64>(),
-                                                   ctx->stream));
-    }
-    u64 totals = 0;
-    ASR_HIP_CHECK(ctx, hipMemcpyAsync(&totals, pre + v, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    ASR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    const i64 vo = (i64)(totals & 0xffffffffu) + (i64)(totals >> 32);
-    *v_out = vo;
+    u64* pre;
+    return coarsen_scan(ctx, keys, v, &pre, v_out);
+}
+int asr_geom_coarsen_fill(asr_hip_context* ctx, const u64* keys, i64 v, u64* out_keys, i64 v_out,
+                          int32_t* up_idx, uint8_t* up_kidx, i64* up_rs) {
+    if (v <= 0) return ASR_HIP_OK;
+    u64* pre;
+    i64 vo;
+    ASR_TRY(coarsen_scan(ctx, keys, v, &pre, &vo));
+    if (vo != v_out) ASR_FAIL(ctx, ASR_HIP_EINVAL, "grid_coarsen_fill: v_out = %lld, the keys give %lld", (long long)v_out,
+                              (long long)vo);
+    // zeroed: keys that break the sorted-unique rule leave positions unplaced, and the up lists index with them
+    int32_t* src = arena_alloc<int32_t>(ctx->scratch, vo);
+    if (!src) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    ASR_HIP_CHECK(ctx, hipMemsetAsync(src, 0, vo * sizeof(int32_t), ctx->stream));
+    return coarsen_lists(ctx, keys, v, pre, vo, src, out_keys, up_idx, up_kidx, up_rs, nullptr, nullptr, nullptr);
+}
+// whole-path variant: the outputs allocated from `keep`
+int asr_geom_coarsen_build(asr_hip_context* ctx, Arena& keep, const u64* keys, i64 v, u64** out_keys, i64* v_out,
+                           int32_t** up_idx, uint8_t** up_kidx, i64** up_rs, int32_t** down_idx, uint8_t** down_kidx,
+                           i64** down_rs) {
+    *v_out = 0;
+    if (v <= 0) return ASR_HIP_OK;
+    u64* pre;
+    ASR_TRY(coarsen_scan(ctx, keys, v, &pre, v_out));
+    const i64 vo = *v_out;
+    int32_t* src = arena_alloc<int32_t>(ctx->scratch, vo);
     *out_keys = arena_alloc<u64>(keep, vo);
     *up_idx = arena_alloc<int32_t>(keep, v);
     *up_kidx = arena_alloc<uint8_t>(keep, v);
@@ -2817,21 +2645,10 @@ int asr_geom_coarsen_build(asr_hip_context* ctx, Arena& keep, const u64* keys, i
     *down_idx = arena_alloc<int32_t>(keep, v);
     *down_kidx = arena_alloc<uint8_t>(keep, v);
     *down_rs = arena_alloc<i64>(keep, vo + 1);
-    i64* cnt = arena_alloc<i64>(ctx->scratch, vo + 1);
-    if (!*out_keys || !*up_idx || !*up_kidx || !*up_rs || !*down_idx || !*down_kidx || !*down_rs || !cnt)
+    if (!src || !*out_keys || !*up_idx || !*up_kidx || !*up_rs || !*down_idx || !*down_kidx || !*down_rs)
         ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-    k_coarsen_place<<<grid_for(v, BLK), BLK, 0, ctx->stream>>>(keys, v, pre, *out_keys, s_s);
-    ASR_CHECK_LAUNCH(ctx);
-    k_coarsen_up<<<grid_for(vo, BLK), BLK, 0, ctx->stream>>>(keys, v, s_s, vo, *up_idx, *up_kidx);
-    ASR_CHECK_LAUNCH(ctx);
-    k_iota64<<<grid_for(v + 1, BLK), BLK, 0, ctx->stream>>>(*up_rs, v + 1);
-    ASR_CHECK_LAUNCH(ctx);
-    k_coarsen_down_count<<<grid_for(vo + 1, BLK), BLK, 0, ctx->stream>>>(keys, v, s_s, vo, cnt);
-    ASR_CHECK_LAUNCH(ctx);
-    ASR_TRY(scan_counts(ctx, ctx->scratch, cnt, *down_rs, vo + 1));
-    k_coarsen_down_fill<<<grid_for(vo, BLK), BLK, 0, ctx->stream>>>(keys, v, s_s, vo, *down_rs, *down_idx, *down_kidx);
-    ASR_CHECK_LAUNCH(ctx);
-    return ASR_HIP_OK;
+    return coarsen_lists(ctx, keys, v, pre, vo, src, *out_keys, *up_idx, *up_kidx, *up_rs, *down_idx, *down_kidx,
+                         *down_rs);
 }
 
 int asr_geom_voxel_info(asr_hip_context* ctx, const asr_octree_frame* frame, const u64* keys,

@@ -204,6 +204,8 @@ int asr_hip_grid_neighbors_rows_fill(asr_hip_context* ctx, const uint64_t* keys_
                                      int32_t* index_out_dev, uint8_t* kernel_index_out_dev);
 
 /* ---- a6: CombineSiblings (cpp/lib/grid.cpp:177-243) ----------------------------------- */
+/* keys: sorted unique voxel keys. count: returns the coarse voxel count; fill: v_out must be that count
+ * (ASR_HIP_EINVAL otherwise). */
 int asr_hip_grid_coarsen_count(asr_hip_context* ctx, const uint64_t* keys_dev, int64_t v,
                                int64_t* v_out);
 int asr_hip_grid_coarsen_fill(asr_hip_context* ctx, const uint64_t* keys_dev, int64_t v,

@@ -93,6 +93,33 @@ def test_grid_hierarchy_bit_exact(case, gpu):
             keys = nxt
 
 
+def test_standalone_grid_operators_equal_the_build(case, gpu):
+    """asr_hip_grid_neighbors_* / asr_hip_grid_coarsen_* on the keys of every grid give the arrays of the build
+    (asr_hip_implicit_build's batched neighbour lists and coarsening); a wrong v_out is an error"""
+    from asr_hip.pipeline import ImplicitPipeline
+    ops = case["ops"]
+    pipe = ImplicitPipeline(synth.make_weights(4, seed=1), device=gpu)
+    pipe.build(case["tpts"], case["trad"], case["bb"][0], case["bb"][1])
+    for i in range(5):
+        keys = pipe.get("voxel_keys%d" % i)
+        got = ops.grid_neighbors(keys)
+        for name, t in zip(("neighbors_index", "neighbors_kernel_index", "neighbors_row_splits"), got):
+            assert np.array_equal(t.cpu().numpy(), pipe.get(name + str(i)).cpu().numpy()), (i, name)
+        if i < 4:
+            got = ops.grid_coarsen(keys)
+            assert np.array_equal(_u64(got[0]), _u64(pipe.get("voxel_keys%d" % (i + 1)))), i
+            for name, t in zip(("up_neighbors_index", "up_neighbors_kernel_index", "up_neighbors_row_splits"), got[1:]):
+                assert np.array_equal(t.cpu().numpy(), pipe.get(name + str(i)).cpu().numpy()), (i, name)
+    keys = pipe.get("voxel_keys3")
+    v, vo = keys.shape[0], int(pipe.sizes.num_voxels[4])
+    ctx = ops.context(gpu)
+    out = torch.empty(vo + 1, dtype=torch.int64, device=gpu)
+    up = [torch.empty(n, dtype=dt, device=gpu) for n, dt in ((v, torch.int32), (v, torch.uint8), (v + 1, torch.int64))]
+    rc = ctx.lib.asr_hip_grid_coarsen_fill(ctx._h, ops.ptr(keys), ctypes.c_int64(v), ops.ptr(out), ctypes.c_int64(vo + 1),
+                                           *(ops.ptr(t) for t in up))
+    assert rc == 1 and b"v_out" in ctx.lib.asr_hip_last_error(ctx._h)
+
+
 @pytest.mark.parametrize("hash_level", [-1, 0, 8], ids=["auto", "binary-search", "hash-to-8"])
 def test_multi_radius_search(case, gpu, hash_level):
     """hash_level: finest level of the search's cell hash table; finer query levels find their cells by binary search in
