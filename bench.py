@@ -16,6 +16,12 @@ asr_hip_implicit_forward_sharded).  The replica mode (one scan per GPU, no colle
 same run and reported as config.replicas; --shard replicas makes it the headline.  The sharded path then runs under a
 watchdog ($ASR_BENCH_ONE_SCAN_TIMEOUT, 420 s): should it fail or not finish on a node, the line falls back to the
 replica measurement and says so.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; the roofline is priced from
+the timed steps' own stage times.  Everything else it can measure runs with --full only, after the timed steps: the
+mesh stage, the raw-scan rate, the other weight set, the f16x2 and exact f32 arithmetics, BASELINE configs C2 / C5 and
+the CPU baseline at N = 1; the instrumented exchange step and config C4 (8 GPUs) of the sharded path.  The --no-* options
+trim a --full run.  At N > 1 a plain run still measures the replicas first: they are the line's fallback.
 """
 import argparse
 import json
@@ -542,12 +548,15 @@ def run_one_scan(args, world, rank, dev, weights, n, barrier, synth, fused=0):
     assert values.shape[0] == sharded.num_voxels[0] and bool(torch.isfinite(values).all())
     if args.dump_outputs and rank == 0 and not fused:
         dump_outputs(args.dump_outputs, values)
-    # one more step, instrumented: bytes and wall time of the halo exchanges
-    st = sharded.instrumented_forward(pts, nrm, radii, bb_min, bb_max)
-    extra = {"halo_bytes_per_step_rank0": {"sent": st["sent_bytes"], "received": st["recv_bytes"]},
-             "exchanges_per_step": st["exchanges"],
-             "exchange_ms_rank0": round(st["seconds"] * 1e3, 3),
-             "exchange_note": "instrumented extra step (device synchronised around every exchange), outside the timed region"}
+    extra = {}
+    if args.full:
+        # one more step, instrumented: bytes and wall time of the halo exchanges
+        st = sharded.instrumented_forward(pts, nrm, radii, bb_min, bb_max)
+        extra = {"halo_bytes_per_step_rank0": {"sent": st["sent_bytes"], "received": st["recv_bytes"]},
+                 "exchanges_per_step": st["exchanges"],
+                 "exchange_ms_rank0": round(st["seconds"] * 1e3, 3),
+                 "exchange_note": "instrumented extra step (device synchronised around every exchange), outside the timed "
+                                  "region"}
     if fallback:
         extra["library_driver_error"] = fallback
     try:
@@ -570,9 +579,12 @@ def main():
     ap.add_argument("--steps", type=int, default=3, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--points", type=int, default=int(os.environ.get("ASR_BENCH_POINTS", 10_000_000)))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every informational measurement (sub-records, other configs, "
+                         "CPU baseline, instrumented exchange step); a plain run measures the headline only")
     ap.add_argument("--cpu-sample", type=int, default=int(os.environ.get("ASR_BENCH_CPU_SAMPLE", 1_000_000)),
                     help="largest C3 slice of the cpu_baseline leg (shrunk to fit its time budget on slow hosts)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--no-pipelined", action="store_true", help="(default now; kept for the profiling scripts)")
     ap.add_argument("--pipelined", action="store_true",
                     help="also run the informational two- / three-context pipelined measurement (slower than the serial "
@@ -590,12 +602,12 @@ def main():
                          "MFMA load; reference = the reference initialisers (models/common_torch.py:57-58), whose forward "
                          "collapses to a near-constant field (SURVEY B.9) and clocks ~10 %% higher -- timed as a sub-record")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the informational runs of BASELINE configs C2 (1 M single-scale continuous conv) and C5 "
-                         "(mixed density, f16 features)")
+                    help="with --full: skip the informational runs of BASELINE configs C2 (1 M single-scale continuous "
+                         "conv) and C5 (mixed density, f16 features)")
     ap.add_argument("--no-other-legs", action="store_true",
-                    help="skip the informational legs on the other weight set and on the f16x2 arithmetic (profiling)")
+                    help="with --full: skip the informational legs on the other weight set and on the f16x2 arithmetic")
     ap.add_argument("--no-exact-f32", action="store_true",
-                    help="skip the informational re-run of the same cloud on the f32-input MFMA kernel (profiling)")
+                    help="with --full: skip the informational re-run of the same cloud on the f32-input MFMA kernel")
     ap.add_argument("--density-variance", type=float, default=1.0,
                     help="10 = the mixed-density cloud of BASELINE config C5")
     ap.add_argument("--shard", choices=["auto", "replicas", "one-scan"], default="auto",
@@ -642,9 +654,15 @@ def main():
     n = args.points
     # released weights are not in the repo.  The timed run uses variance-preserving seeded weights: with the
     # reference initialisers the forward collapses to a near-constant field and the chip clocks higher than
-    # under real MFMA load; that leg is timed as a sub-record.
-    weights_ref = synth.make_weights(1, seed=0, init="reference")
-    weights = synth.make_weights(1, seed=2) if args.weights == "variance" else weights_ref
+    # under real MFMA load; that leg is timed as a sub-record (--full).  A weight set takes 1-2 s of host time: each is made
+    # when it is needed.
+    def weights_variance():
+        return synth.make_weights(1, seed=2)
+
+    def weights_ref():
+        return synth.make_weights(1, seed=0, init="reference")
+
+    weights = weights_variance() if args.weights == "variance" else weights_ref()
     shapes = synth.unet5_param_shapes(1)
     mode = args.shard
     if mode == "auto":
@@ -693,7 +711,7 @@ def main():
     values_timed = values.clone()  # `values` lives in the context arena until the next forward
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, values_timed)
-    mesh_info = mesh_stage(pipe, synth) if rank == 0 else None
+    mesh_info = mesh_stage(pipe, synth) if rank == 0 and args.full else None
     pipelined = None
     if world == 1 and args.pipelined and not args.no_pipelined:
         pipelined = [pipelined_rate(pipe, weights, dev, (pts, nrm, radii, bb_min, bb_max), n, max(6, 2 * args.steps), d)
@@ -701,20 +719,22 @@ def main():
 
     # raw-scan rate (outside `value`: the metric takes radii as inputs): the exact 24-NN radius
     # estimate of the pre-filter (cpp/lib/preprocess.cpp:25-39) on the GPU, steady state (second call), + one step
-    t_knn2 = time.perf_counter()
-    synth.knn_radii_gpu(pts, 24)
-    torch.cuda.synchronize()
-    t_knn2 = time.perf_counter() - t_knn2
+    t_knn2 = None
+    if args.full:
+        t_knn2 = time.perf_counter()
+        synth.knn_radii_gpu(pts, 24)
+        torch.cuda.synchronize()
+        t_knn2 = time.perf_counter() - t_knn2
     exact = other_weights = f16x2 = None
     inputs = (pts, nrm, radii, bb_min, bb_max)
-    if world == 1 and args.precision in SPLIT_PRODUCTS and not args.no_exact_f32:
+    if world == 1 and args.full and args.precision in SPLIT_PRODUCTS and not args.no_exact_f32:
         exact = exact_f32_run(weights, dev, inputs, n, max(args.steps, 2), shapes, values_timed)
         exact["weights"] = args.weights
         exact["timed_arithmetic_vs_this_kernel"] = deviation_check(dev, inputs, args.precision, synth)
-    if world == 1 and rank == 0 and not args.no_other_legs:
+    if world == 1 and rank == 0 and args.full and not args.no_other_legs:
         # the other weight set on the timed arithmetic (bounds the clock / data effect of DESIGN 7.4), and the narrower
         # f16x2 arithmetic on the timed weights (a labelled sub-record: not creditable as an fp32 result)
-        ow = weights_ref if args.weights == "variance" else synth.make_weights(1, seed=2)
+        ow = weights_ref() if args.weights == "variance" else weights_variance()
         other_weights = timed_leg(ow, dev, inputs, n, max(args.steps // 2, 3), args.precision, shapes)
         other_weights["weights"] = ("reference initialisers uniform(-0.05, 0.05), zero bias (models/common_torch.py:57-58): the "
                                     "forward collapses to a near-constant field, SURVEY B.9" if args.weights == "variance"
@@ -725,7 +745,7 @@ def main():
             f16x2["weights"] = args.weights
             f16x2["vs_exact_f32_kernel"] = deviation_check(dev, inputs, "f16x2", synth)
     c2 = c5 = None
-    if world == 1 and rank == 0 and not args.no_other_configs and args.density_variance == 1.0:
+    if world == 1 and rank == 0 and args.full and not args.no_other_configs and args.density_variance == 1.0:
         c2 = config_c2(dev, synth)
         if args.precision != "f16":
             c5 = config_c5(dev, weights, synth, n)
@@ -768,20 +788,23 @@ def main():
                        "agg_pairs": int(pipe.sizes.num_agg_pairs),
                        "parallelism": "one scan per GPU, no collective on the data path",
                        "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
-                       "untimed_knn24_radii_ms": round(t_knn * 1e3, 1),
-                       "untimed_raw_scan": {"knn24_radii_ms_steady": round(t_knn2 * 1e3, 1),
-                                            "points_per_s_with_knn_radii": n / (t_knn2 + dt / steps),
-                                            "note": "pre-filter radius estimate + one step; radii are inputs of the "
-                                                    "metric, this is the rate from a raw scan"},
-                       "untimed_mesh_stage": mesh_info,
-                       "untimed_config_c2_single_scale_cconv_1m": c2,
-                       "untimed_config_c5_mixed_density_f16": c5,
-                       "untimed_pipelined_two_contexts": pipelined,
-                       "untimed_other_weight_set": other_weights,
-                       "untimed_f16x2_narrower_arithmetic": f16x2,
-                       "untimed_exact_f32_kernel": exact},
+                       "untimed_knn24_radii_ms": round(t_knn * 1e3, 1)},
             "roofline": None,
         }
+        if args.full or pipelined is not None:
+            out["config"]["untimed_pipelined_two_contexts"] = pipelined
+        if args.full:
+            out["config"].update({
+                "untimed_raw_scan": {"knn24_radii_ms_steady": round(t_knn2 * 1e3, 1),
+                                     "points_per_s_with_knn_radii": n / (t_knn2 + dt / steps),
+                                     "note": "pre-filter radius estimate + one step; radii are inputs of the "
+                                             "metric, this is the rate from a raw scan"},
+                "untimed_mesh_stage": mesh_info,
+                "untimed_config_c2_single_scale_cconv_1m": c2,
+                "untimed_config_c5_mixed_density_f16": c5,
+                "untimed_other_weight_set": other_weights,
+                "untimed_f16x2_narrower_arithmetic": f16x2,
+                "untimed_exact_f32_kernel": exact})
         out["arithmetic"] = ARITHMETIC[args.precision]
         # the dominant kernel against BOTH roofs; `bound` = the one it sits closer to.  MFMA: algorithmic FLOP over the
         # dtype's dense peak (/ products per algorithmic product).  HBM: `achieved` = ALGORITHMIC bytes (SURVEY section 6
@@ -890,7 +913,7 @@ def main():
             one_scan_error = "the sharded one-scan path failed on another rank"
             one_scan_out = None
         # config C4 (8 GPUs: eight fused scans, 80 M points, sharded): informational sub-record, its own watchdog
-        if not any_failed and (world == 8 or os.environ.get("ASR_BENCH_C4")):
+        if not any_failed and args.full and (world == 8 or os.environ.get("ASR_BENCH_C4")):
             limit4 = float(os.environ.get("ASR_BENCH_C4_TIMEOUT", 300))
             watchdog = watchdog_for("config C4 (fused scans, sharded)", limit4, one_scan_out)
             try:
@@ -907,7 +930,7 @@ def main():
 
     if rank == 0:
         out = final_line(one_scan_out, one_scan_error, c4_out)
-        if not args.no_cpu_baseline and world == 1:  # reported baseline: rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported baseline: rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, 1000)
         print(json.dumps(out))
     if world > 1:
