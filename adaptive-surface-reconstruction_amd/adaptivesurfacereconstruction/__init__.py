@@ -175,11 +175,17 @@ def _load_weights(weights):
 def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point_radius_scale=1.0,
                         density_percentile_threshold=10.0, point_radius_estimation_knn=24,
                         octree_max_depth=21, contouring_value_threshold=1.0,
-                        keep_n_connected_components=2**63 - 1, minimum_component_size=3, *, weights=None):
+                        keep_n_connected_components=2**63 - 1, minimum_component_size=3, *, weights=None,
+                        precision="f32"):
     """module.cpp:58-109,291-346 -> asr::ReconstructSurface (cpp/lib/asr.cpp:95-349): pre-filter,
     implicit values, dual contouring, component filter; every stage on the MI355X.
-    `weights` (keyword only) replaces the reference's bundled model.pt, see _load_weights."""
+    `weights` (keyword only) replaces the reference's bundled model.pt, see _load_weights.
+    `precision` (keyword only): arithmetic of the network's sparse convolutions, one of asr_hip._lib.PRECISIONS --
+    "f32" (default, the reference's arithmetic), "bf16x3_2acc" (bf16 matrix cores, a third of the f32 arithmetic's
+    rms error, half its U-Net time), "bf16x3", "f16x2" or "f16" (see asr_hip.pipeline.ImplicitPipeline)."""
     from asr_hip.pipeline import ImplicitPipeline
+    if precision not in _lib.PRECISIONS:
+        raise ValueError("precision must be one of %s" % ", ".join(sorted(_lib.PRECISIONS)))
     points = _f32(points, "points", "[num_points,3]", 2, 3)
     normals = _f32(normals, "normals", "[num_points,3]", 2, 3)
     radii = np.ascontiguousarray(radii, dtype=np.float32)
@@ -207,7 +213,7 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
     dev = torch.device("cuda")
     pipe = ImplicitPipeline(_load_weights(weights), device="cuda:%d" % torch.cuda.current_device(),
                             point_radius_scale=point_radius_scale, octree_max_depth=octree_max_depth,
-                            scale_sdf=True)
+                            scale_sdf=True, precision=precision)
     # exact bounding box of the filtered points (asr.cpp:148-150; quirk B.1 applies)
     bb_min, bb_max = points.min(0), points.max(0)
     pipe.forward(torch.from_numpy(points).to(dev), torch.from_numpy(normals).to(dev),

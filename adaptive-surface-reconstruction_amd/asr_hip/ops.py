@@ -401,7 +401,8 @@ def sparse_conv(filters, inp_features, neighbors_index, neighbors_kernel_index,
 
 def pack_filters(filters, mode, filters_b=None):
     """re-packed 16-bit copy of a filter tensor [K, cin, cout] (+ second bank [K, cin, cout_b]) for
-    sparse_conv16 (asr_hip_sparse_conv_pack); mode: "f16", "bf16x3" or "f16x2".  Pack once per weight tensor."""
+    sparse_conv16 (asr_hip_sparse_conv_pack); mode: "f16", "bf16x3", "bf16x3_2acc" or "f16x2" ("bf16x3_2acc" packs the
+    same bytes as "bf16x3").  Pack once per weight tensor."""
     m = _lib.PRECISIONS[mode]
     filters = _dev(filters, torch.float32)
     fb = _dev(filters_b, torch.float32) if filters_b is not None else None
@@ -454,9 +455,9 @@ def sparse_conv16(mode, packed, kernel_size, cin, cout, inp_features, neighbors_
                   out=None, out_dtype=None, return_importance=False, neighbors_importance=None, row_perm=None,
                   num_rows=None, cout_b=0, bias_b=None, force_nt=0, force_waves=0, plan=None, inp_absmax=None,
                   out_absmax=None):
-    """SpecialSparseConv.forward on the 16-bit matrix cores (asr_hip_sparse_conv_f16 / _bf16x3 / _f16x2).
+    """SpecialSparseConv.forward on the 16-bit matrix cores (asr_hip_sparse_conv_f16 / _bf16x3 / _bf16x3_2acc / _f16x2).
     mode "f16": inp_features / residual are float16 tensors, out is float16 (default) or float32;
-    mode "bf16x3" / "f16x2": float32 in and out, fp32-class result.  packed: pack_filters(filters, mode[, filters_b]).
+    mode "bf16x3" / "bf16x3_2acc" / "f16x2": float32 in and out, fp32-class result.  packed: pack_filters(filters, mode[, filters_b]).
     plan: ConvPlan of this list (one is built for the call otherwise).
     inp_absmax / out_absmax: int32 device scalars with the f32 bits of the largest |element| of the input (f16x2; None:
     computed by one pass) and the running maximum of what is written to out (new_absmax(); the caller zeroes it)."""
@@ -516,6 +517,8 @@ def sparse_conv16(mode, packed, kernel_size, cin, cout, inp_features, neighbors_
         ctx.call("asr_hip_sparse_conv_f16", ctypes.byref(a), ptr(packed), int(out.dtype == torch.float16))
     elif mode == "f16x2":
         ctx.call("asr_hip_sparse_conv_f16x2", ctypes.byref(a), ptr(packed))
+    elif mode == "bf16x3_2acc":
+        ctx.call("asr_hip_sparse_conv_bf16x3_2acc", ctypes.byref(a), ptr(packed))
     else:
         ctx.call("asr_hip_sparse_conv_bf16x3", ctypes.byref(a), ptr(packed))
     return (out, oimp) if return_importance else out

@@ -54,7 +54,8 @@ class ImplicitPipeline:
                  scale_sdf=True, precision="f32"):
         """precision: arithmetic of the 53 sparse convs -- "f32" (exact f32 MFMA, the reference's type),
         "f16" (f16 activations and weights, f32 accumulate: BASELINE config C5), "bf16x3" (exact three-way
-        bf16 split on the bf16 matrix cores, six MFMAs per product: fp32-class results) or "f16x2" (per-tensor
+        bf16 split on the bf16 matrix cores, six MFMAs per product: fp32-class results), "bf16x3_2acc" (bf16x3 with a
+        second accumulator for the five small products: below the exact f32 kernel's error) or "f16x2" (per-tensor
         power-of-two scaling + two-way f16 split, three MFMAs per product: fp32-class results, what bench.py times)"""
         if precision not in _lib.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(_lib.PRECISIONS))

@@ -453,15 +453,16 @@ class ShardedNetwork:
 
 # ---- GPU backend: the C ABI through asr_hip.ops --------------------------------------------------------
 class HipBackend:
-    """precision "f32": the exact f32 MFMA kernel; "bf16x3" / "f16x2": the plan-driven 16-bit kernel (fp32-class).
+    """precision "f32": the exact f32 MFMA kernel; "bf16x3" / "bf16x3_2acc" / "f16x2": the plan-driven 16-bit kernel
+    (fp32-class).
     Either way a row is computed by the same kernel arithmetic as on one GPU, so sharded results equal the unsharded
     pipeline of the same precision bit for bit.  f16x2 scales every activation tensor by a power of two taken from its
     largest magnitude over ALL rows: each rank's convolution keeps the maximum of the rows it writes (out_absmax) and
     one MAX all-reduce of that scalar per convolution makes it the tensor's (group: the ranks that share the cloud)."""
 
     def __init__(self, device, precision="f32", group=None):
-        if precision not in ("f32", "bf16x3", "f16x2"):
-            raise ValueError("HipBackend: precision must be 'f32', 'bf16x3' or 'f16x2'")
+        if precision not in ("f32", "bf16x3", "bf16x3_2acc", "f16x2"):
+            raise ValueError("HipBackend: precision must be 'f32', 'bf16x3', 'bf16x3_2acc' or 'f16x2'")
         self.device = torch.device(device)
         self.precision = precision
         self.group = group

@@ -2,7 +2,7 @@
 reference (cpp/bin/main.cpp:114-177: `asrtool --in point_cloud.ply --out mesh.ply`, `--version`,
 `--third-party-notices`) on top of adaptivesurfacereconstruction.reconstruct_surface.
 
-    python adaptive-surface-reconstruction_amd/asrtool.py --in scan.ply --out mesh.ply [--weights model.pt]
+    python adaptive-surface-reconstruction_amd/asrtool.py --in scan.ply --out mesh.ply [--weights model.pt] [--precision NAME]
 
 The reference bundles its network as <resource dir>/model.pt (cpp/lib/asr.cpp:138-139); here the weights come
 from --weights (a TorchScript archive with the same tensor names, a pickled state dict or an .npz) or from
@@ -19,6 +19,7 @@ Arguments:
 
 Options:
     --weights FILE  Network weights (TorchScript model.pt, state dict .pt or .npz); default $ASR_RESOURCE_DIR
+    --precision NAME  Arithmetic of the network's sparse convolutions: f32 (default), bf16x3_2acc, bf16x3, f16x2, f16
     --version  Prints the version information
     --third-party-notices  Prints third-party software notices
 """
@@ -48,12 +49,17 @@ def main(argv=None):
     if inp is None or out is None:
         sys.stdout.write(HELP)
         return 1
+    precision = _option(argv, "--precision") or "f32"
+    from asr_hip import _lib
+    if precision not in _lib.PRECISIONS:
+        sys.stderr.write("asrtool: unknown precision '%s' (one of %s)\n" % (precision, ", ".join(sorted(_lib.PRECISIONS))))
+        return 1
     import adaptivesurfacereconstruction as asr
     from asr_hip import ply
     print("reading points")
     points, normals, radii = ply.read_points(inp)
     print("%d / %d" % (len(points), len(points)))
-    result = asr.reconstruct_surface(points, normals, radii, weights=_option(argv, "--weights"))
+    result = asr.reconstruct_surface(points, normals, radii, weights=_option(argv, "--weights"), precision=precision)
     ply.write_mesh(out, result["vertices"], result["triangles"])
     print("wrote %s: %d vertices, %d triangles" % (out, len(result["vertices"]), len(result["triangles"])))
     return 0

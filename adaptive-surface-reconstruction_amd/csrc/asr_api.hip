@@ -512,7 +512,8 @@ int asr_hip_sparse_conv_f32(asr_hip_context* ctx, const asr_sparse_conv_args* a)
     return asr_conv_sparse(ctx, a);
 }
 size_t asr_hip_sparse_conv_packed_bytes(int mode, int K, int cin, int cout, int cout_b) {
-    if ((mode != ASR_CONV16_F16 && mode != ASR_CONV16_BF16X3 && mode != ASR_CONV16_F16X2) || K < 1 || cin < 1 || cout < 1 ||
+    if ((mode != ASR_CONV16_F16 && mode != ASR_CONV16_BF16X3 && mode != ASR_CONV16_F16X2 && mode != ASR_CONV16_BF16X3_2ACC) ||
+        K < 1 || cin < 1 || cout < 1 ||
         cout_b < 0)
         return 0;
     return asr_conv16_packed_bytes(mode, K, cin, cout, cout_b);
@@ -603,6 +604,10 @@ int asr_hip_sparse_conv_bf16x3(asr_hip_context* ctx, const asr_sparse_conv_args*
 int asr_hip_sparse_conv_f16x2(asr_hip_context* ctx, const asr_sparse_conv_args* a, const void* packed) {
     CTX_GUARD(ctx);
     return conv16_entry(ctx, a, packed, ASR_CONV16_F16X2, 0);
+}
+int asr_hip_sparse_conv_bf16x3_2acc(asr_hip_context* ctx, const asr_sparse_conv_args* a, const void* packed) {
+    CTX_GUARD(ctx);
+    return conv16_entry(ctx, a, packed, ASR_CONV16_BF16X3_2ACC, 0);
 }
 int asr_hip_absmax_f32(asr_hip_context* ctx, const float* x, int64_t rows, int cols, int64_t ld, uint32_t* out) {
     CTX_GUARD(ctx);
@@ -701,7 +706,8 @@ struct Feat {
 struct Net {
     asr_hip_context* ctx;
     WeightTable wt;
-    int precision = 0;  // 0 = exact f32 MFMA, ASR_CONV16_F16, ASR_CONV16_BF16X3, ASR_CONV16_F16X2 (asr_implicit_params.precision)
+    int precision = 0;  // 0 = exact f32 MFMA, ASR_CONV16_F16, ASR_CONV16_BF16X3, ASR_CONV16_F16X2, ASR_CONV16_BF16X3_2ACC
+                        // (asr_implicit_params.precision)
     int num_amax = 0;
     // sharded forward (ctx->shard): importance arrays are valid on the owned rows only and travel with the halo of the
     // features -- except this one, the aggregation's per-pair array, which every rank holds in full (quirk B.2)
@@ -1381,9 +1387,10 @@ int implicit_aggregate(asr_hip_context* ctx, const float* points, const float* n
     ctx->scratch.reset();
     if (ctx->build_mark_ok) arena_rewind(ctx->persist, ctx->build_mark);
     if (net.precision != 0 && net.precision != ASR_CONV16_F16 && net.precision != ASR_CONV16_BF16X3 &&
-        net.precision != ASR_CONV16_F16X2)
+        net.precision != ASR_CONV16_F16X2 && net.precision != ASR_CONV16_BF16X3_2ACC)
         ASR_FAIL(ctx, ASR_HIP_EINVAL,
-                 "implicit_network: precision must be 0, ASR_CONV16_F16, ASR_CONV16_BF16X3 or ASR_CONV16_F16X2");
+                 "implicit_network: precision must be 0, ASR_CONV16_F16, ASR_CONV16_BF16X3, ASR_CONV16_F16X2 or "
+                 "ASR_CONV16_BF16X3_2ACC");
     GridDev* g = ctx->grids;
     const i64 V0 = g[0].v;
     const i64 P = ctx->sizes.num_agg_pairs;
@@ -1668,7 +1675,7 @@ int asr_hip_implicit_forward_sharded(asr_hip_context* ctx, const asr_shard_comm*
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "implicit_forward_sharded: points is null!");  // cpp/lib/asr.cpp:101-103
     if (prm->precision == ASR_CONV16_F16)
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "implicit_forward_sharded: the f16-activation network is not sharded (precision 0, "
-                                      "ASR_CONV16_BF16X3 or ASR_CONV16_F16X2)");
+                                      "ASR_CONV16_BF16X3, ASR_CONV16_F16X2 or ASR_CONV16_BF16X3_2ACC)");
     if (!ctx->opt.build_search) ASR_FAIL(ctx, ASR_HIP_EINVAL, "implicit_forward_sharded needs option build_search");
     // option shard_geometry: 0 = the whole cloud's geometry on every rank (overlapped search, as on one GPU), 1 = lists,
     // plans and search for the owned voxels only, -1 (default) = 1 whenever there is more than one rank

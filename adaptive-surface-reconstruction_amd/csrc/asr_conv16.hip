@@ -10,6 +10,11 @@
 //                      one fp32 rounding.  6 MFMAs at 16x the f32-MFMA rate = 2.7x the f32 matrix peak for
 //                      the same algorithmic FLOP.
 //
+//   ASR_CONV16_BF16X3_2ACC  the operands, packed filters and six products of bf16x3, accumulated in two chains: the
+//                      leading product a0*b0 goes to the running sum, the five small ones to a second accumulator that
+//                      is added to it once, before the epilogue (see sconv16_products).  rms error 3x below the
+//                      exact-f32 kernel's, no bias; 32 more registers on the 128-column instances.
+//
 //   ASR_CONV16_F16X2   fp32-class results from HALF the MFMAs of bf16x3: both operands are scaled by a power of two
 //                      (per tensor: the largest magnitude goes to [2^14, 2^15), exact) and split into two f16
 //                      terms (a = a0 + a1, 11 mantissa bits each, round to nearest), a*b = a0*b0 + a1*b0 + a0*b1.
@@ -38,6 +43,9 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef uint16_t u16;
 
 constexpr int NBR_LD = 57;
+
+// the modes whose operands are the exact three-way bf16 split (three weight planes, f32 activations)
+constexpr bool is_bf16x3(int mode) { return mode == ASR_CONV16_BF16X3 || mode == ASR_CONV16_BF16X3_2ACC; }
 
 __device__ inline u16 f32_to_bf16_bits(float x) {  // round to nearest even
     const f32x2 v = {x, 0.f};
@@ -163,17 +171,15 @@ __device__ __forceinline__ void sconv16_split_f16x2(const u32x4& q0, const u32x4
 // column tile (bank a's last eight columns and bank b's eight) go to tacc[0] ONLY; at the end of the slot it is added to
 // acc[NT - 1] as it is (bank a) and, scaled per row by the importance, to acc_b (bank b) -- not a second chain of products.
 // ------------------------------------------------------------------------------------------
-// -DASR_BF16X3_CHAIN=4 (build-time, off): bf16x3 with a SECOND accumulator for the five small products of a step, added once in
-// the epilogue.  The default chain rounds the large running sum six times per (slot, panel) step, which is where bf16x3's
-// error comes from (scripts/split_error_study.py: rms error of `values` 2.1e-7 of the range -> 6.3e-8, below the
-// exact-f32 kernel's 1.9e-7); it costs 32 registers on the 128-column instances = two blocks per CU instead of three,
-// U-Net 26.4 -> 27.5 ms at 10 M points, so the default stays the single chain.
-#ifndef ASR_BF16X3_CHAIN
-#define ASR_BF16X3_CHAIN 0
-#endif
-template <int NT, int KC, int MODE, bool IMP, bool DUAL, int PLANES, int NJ>
+// ASR_CONV16_BF16X3_2ACC: the same six products in two chains.  The five small ones (2^-8 and 2^-16 of the leading one) go
+// to a second accumulator lo that is added to acc ONCE, before the epilogue: one fp32 rounding at the running sum's magnitude
+// per step instead of six, which is where bf16x3's error comes from.  Tiles whose products are summed per slot from
+// zero (IMP, and DUAL's bank-b tile) keep the single chain of bf16x3.  DUAL has no lo[NT - 1]: in the column chunks without
+// bank b the last tile's small products go to tacc[0], which only the bank-b chunk uses otherwise.  Which chain a product
+// goes to depends on its column and the layer kind only, never on NT, WAVES or the kernel.
+template <int NT, int KC, int MODE, bool IMP, bool DUAL, int PLANES, int NJ, int NL>
 __device__ inline void sconv16_products(const u32x4 (&fa)[NJ][PLANES], const u32x4* __restrict__ sb, f32x4 (&acc)[NT],
-                                        f32x4 (&tacc)[IMP ? NT : 1], bool has_b, int ncol, int g, f32x4 (&lo)[NT]) {
+                                        f32x4 (&tacc)[IMP ? NT : 1], bool has_b, int ncol, int g, f32x4 (&lo)[NL]) {
     constexpr int SLOTS = KC / 8;
     constexpr int PLANE_PIECES = NT * 16 * SLOTS;
 #pragma unroll
@@ -238,34 +244,42 @@ __device__ inline void sconv16_products(const u32x4 (&fa)[NJ][PLANES], const u32
     }
                 if (IMP) {
                     ASR_SIX(tacc[nb])
-                } else {
-#if ASR_BF16X3_CHAIN == 4
-                    if (DUAL && has_b && nb == NT - 1) {
-                        ASR_SIX(tacc[0])
-                    } else
-                    // the five small products (2^-8 and 2^-16 of the leading one) go to a second accumulator that is added
-                    // ONCE, in the epilogue: one fp32 rounding at the running sum's magnitude per step instead of six
-                    {
-                        const bf16x8 b2 = __builtin_bit_cast(bf16x8, sb[2 * PLANE_PIECES + piece]);
-                        lo[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b2, lo[nb], 0, 0, 0);
-                        const bf16x8 b1 = __builtin_bit_cast(bf16x8, sb[PLANE_PIECES + piece]);
-                        lo[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, lo[nb], 0, 0, 0);
-                        lo[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b1, lo[nb], 0, 0, 0);
-                        const bf16x8 b0 = __builtin_bit_cast(bf16x8, sb[piece]);
-                        lo[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b0, lo[nb], 0, 0, 0);
-                        lo[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b0, lo[nb], 0, 0, 0);
+                } else if constexpr (MODE == ASR_CONV16_BF16X3_2ACC) {
+                    // DUAL's last tile: tacc[0] (bank-b chunk: all six, the order of ASR_SIX; other chunks: the small five)
+                    f32x4& l = DUAL && nb == NT - 1 ? tacc[0] : lo[nb < NL ? nb : 0];
+                    const bf16x8 b2 = __builtin_bit_cast(bf16x8, sb[2 * PLANE_PIECES + piece]);
+                    l = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b2, l, 0, 0, 0);
+                    const bf16x8 b1 = __builtin_bit_cast(bf16x8, sb[PLANE_PIECES + piece]);
+                    l = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, l, 0, 0, 0);
+                    l = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b1, l, 0, 0, 0);
+                    const bf16x8 b0 = __builtin_bit_cast(bf16x8, sb[piece]);
+                    l = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b0, l, 0, 0, 0);
+                    l = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b0, l, 0, 0, 0);
+                    if (DUAL && has_b && nb == NT - 1)
+                        tacc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, tacc[0], 0, 0, 0);
+                    else
                         acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[nb], 0, 0, 0);
-                    }
-#else
-                    if (DUAL && has_b && nb == NT - 1) {
-                        ASR_SIX(tacc[0])
-                    } else {
-                        ASR_SIX(acc[nb])
-                    }
-#endif
+                } else if (DUAL && has_b && nb == NT - 1) {
+                    ASR_SIX(tacc[0])
+                } else {
+                    ASR_SIX(acc[nb])
                 }
 #undef ASR_SIX
             }
+        }
+    }
+}
+
+// ASR_CONV16_BF16X3_2ACC, after the last step: the small products' accumulator into the running sum, one addition per element
+// (DUAL: tacc[0] holds the last tile's in the chunks without bank b; in the bank-b chunk it was folded per slot)
+template <int NT, bool DUAL, int NL>
+__device__ inline void sconv16_fold_lo(f32x4 (&acc)[NT], const f32x4 (&lo)[NL], const f32x4& tacc0, bool has_b) {
+#pragma unroll
+    for (int nb = 0; nb < NT; ++nb) {
+        if (DUAL && nb == NT - 1) {
+            if (!has_b) acc[nb] += tacc0;
+        } else {
+            acc[nb] += lo[nb];
         }
     }
 }
@@ -361,7 +375,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? 2 : 3) void k_sconv_mfma16
     constexpr int TM = WAVES * 16;
     constexpr int NTHR = WAVES * 64;
     constexpr int NCOL = NT * 16;
-    constexpr int PLANES = MODE == ASR_CONV16_BF16X3 ? 3 : (MODE == ASR_CONV16_F16X2 ? 2 : 1);
+    constexpr int PLANES = is_bf16x3(MODE) ? 3 : (MODE == ASR_CONV16_F16X2 ? 2 : 1);
     constexpr int SLOTS = KC / 8;                 // 16-byte pieces per panel row
     constexpr int NJ = KC / 32;                   // MFMA k-chunks per panel
     constexpr int PV = PLANES * NCOL * SLOTS;     // 16-byte pieces per panel
@@ -458,9 +472,12 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? 2 : 3) void k_sconv_mfma16
     bmask &= (1ull << K) - 1;
 
     f32x4 acc[NT];
-    f32x4 lo[NT];  // (ASR_BF16X3_CHAIN == 4: the small products' accumulator; unused and removed otherwise)
+    // ASR_CONV16_BF16X3_2ACC: the small products' accumulator (see sconv16_products).  The other modes never touch it and
+    // it is removed; it keeps its old size there because the size alone shifts the register assignment of their DUAL code
+    constexpr int NL = MODE != ASR_CONV16_BF16X3_2ACC ? NT : (DUAL && NT > 1 ? NT - 1 : NT);
+    f32x4 lo[NL];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) lo[t] = {0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < NL; ++t) lo[t] = {0.f, 0.f, 0.f, 0.f};
     f32x4 tacc[IMP ? NT : 1];  // per-slot accumulators of the importance-weighted bank
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
@@ -631,7 +648,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? 2 : 3) void k_sconv_mfma16
         if (active) {
             const u32x4* sb = s_B[buf];
             __builtin_amdgcn_s_setprio(1);
-            sconv16_products<NT, KC, MODE, IMP, DUAL, PLANES, NJ>(fa, sb, acc, tacc, has_b, ncol, g, lo);
+            sconv16_products<NT, KC, MODE, IMP, DUAL, PLANES, NJ, NL>(fa, sb, acc, tacc, has_b, ncol, g, lo);
             __builtin_amdgcn_s_setprio(0);
             // end of a slot: scale the slot's importance-weighted products per row and fold them in
             if ((IMP || DUAL) && p_cur == npanel - 1) {
@@ -673,10 +690,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? 2 : 3) void k_sconv_mfma16
         rows4[i] = s_row[wave * 16 + 4 * g + i];
         norms4[i] = s_norm[wave * 16 + 4 * g + i];
     }
-#if ASR_BF16X3_CHAIN == 4
-#pragma unroll
-    for (int nb = 0; nb < NT; ++nb) acc[nb] += lo[nb];
-#endif
+    if constexpr (MODE == ASR_CONV16_BF16X3_2ACC && !IMP) sconv16_fold_lo<NT, DUAL, NL>(acc, lo, tacc[0], has_b);
     sconv16_epilogue<NT, MODE, DUAL>(a, acc, acc_b, rows4, norms4, n0, ncol, ca, cout, has_b, out_f16, zeros, unscale);
     if (a.out_importance && ychunk == 0 && tid < TM && s_row[tid] >= 0)
         a.out_importance[s_row[tid]] = s_norm[tid];
@@ -751,13 +765,15 @@ constexpr bool plan_line() {
     return plan_ldma<NT, KC, WAVES, MODE, IMP, DUAL>() ||
            (ASR_PLAN_LINEGATHER && MODE != ASR_CONV16_F16 && KC == 32 && (NT <= 2 || (NT == 4 && WAVES == 8 && (IMP || DUAL))));
 }
+// (bf16x3_2acc: its second accumulator holds the 8-wave instances to two blocks per CU, i.e. 128 registers -- DESIGN 4.3)
 template <int NT, int KC, int WAVES, int MODE, bool IMP, bool DUAL, bool SPLIT = false>
-__global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? (NT >= 8 && (IMP || DUAL) ? 2 : 3) : 4) void k_sconv_plan16(
+__global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? (MODE == ASR_CONV16_BF16X3_2ACC ? 4 : (NT >= 8 && (IMP || DUAL) ? 2 : 3)) : 4)
+void k_sconv_plan16(
         asr_sparse_conv_args a, asr_conv_plan_view plan, const u16* __restrict__ packed, int cin_pad, int ctot_pad, int out_f16,
         const float* __restrict__ zeros, asr_split_args sp) {
     constexpr int TM = WAVES * 16;
     constexpr int NCOL = NT * 16;
-    constexpr int PLANES = MODE == ASR_CONV16_BF16X3 ? 3 : (MODE == ASR_CONV16_F16X2 ? 2 : 1);
+    constexpr int PLANES = is_bf16x3(MODE) ? 3 : (MODE == ASR_CONV16_F16X2 ? 2 : 1);
     constexpr int SLOTS = KC / 8;
     constexpr int NJ = KC / 32;
     constexpr int PV = PLANES * NCOL * SLOTS;  // 16-byte pieces per panel
@@ -830,9 +846,12 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? (NT >= 8 && (IMP || DUAL) 
     }
 
     f32x4 acc[NT];
-    f32x4 lo[NT];  // (ASR_BF16X3_CHAIN == 4: the small products' accumulator; unused and removed otherwise)
+    // ASR_CONV16_BF16X3_2ACC: the small products' accumulator (see sconv16_products).  The other modes never touch it and
+    // it is removed; it keeps its old size there because the size alone shifts the register assignment of their DUAL code
+    constexpr int NL = MODE != ASR_CONV16_BF16X3_2ACC ? NT : (DUAL && NT > 1 ? NT - 1 : NT);
+    f32x4 lo[NL];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) lo[t] = {0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < NL; ++t) lo[t] = {0.f, 0.f, 0.f, 0.f};
     f32x4 tacc[IMP ? NT : 1];
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
@@ -1098,7 +1117,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? (NT >= 8 && (IMP || DUAL) 
         if (active) {
             const u32x4* sb = BUF ? s_B1 : s_B0;
             __builtin_amdgcn_s_setprio(1);
-            sconv16_products<NT, KC, MODE, IMP, DUAL, PLANES, NJ>(fa, sb, acc, tacc, has_b, ncol, g, lo);
+            sconv16_products<NT, KC, MODE, IMP, DUAL, PLANES, NJ, NL>(fa, sb, acc, tacc, has_b, ncol, g, lo);
             __builtin_amdgcn_s_setprio(0);
             if (ROWW && roww && slot_end) {
 #pragma unroll
@@ -1137,10 +1156,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? (NT >= 8 && (IMP || DUAL) 
     }
 #undef ASR_SEQ_ADVANCE
 
-#if ASR_BF16X3_CHAIN == 4
-#pragma unroll
-    for (int nb = 0; nb < NT; ++nb) acc[nb] += lo[nb];
-#endif
+    if constexpr (MODE == ASR_CONV16_BF16X3_2ACC && !IMP) sconv16_fold_lo<NT, DUAL, NL>(acc, lo, tacc[0], has_b);
     // output rows of this lane's four accumulator rows (-1: beyond the list)
     int q4[4];
 #pragma unroll
@@ -1258,11 +1274,11 @@ static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 // f16 tensors whose padded cin is a multiple of 64 use 64-deep panels (bf16x3 panels carry three planes)
 static inline int panel_depth(int mode, int cin) { return mode == ASR_CONV16_F16 && round_up(cin, 32) % 64 == 0 ? 64 : 32; }
 
-static inline bool mode_ok(int mode) { return mode == ASR_CONV16_F16 || mode == ASR_CONV16_BF16X3 || mode == ASR_CONV16_F16X2; }
+static inline bool mode_ok(int mode) { return mode == ASR_CONV16_F16 || is_bf16x3(mode) || mode == ASR_CONV16_F16X2; }
 
 // f16x2: two planes + a 16-byte trailer: [0] the exponent of the weights' power-of-two scale, [1] their largest magnitude
 size_t asr_conv16_packed_bytes(int mode, int K, int cin, int cout, int cout_b) {
-    const size_t planes = mode == ASR_CONV16_BF16X3 ? 3 : (mode == ASR_CONV16_F16X2 ? 2 : 1);
+    const size_t planes = is_bf16x3(mode) ? 3 : (mode == ASR_CONV16_F16X2 ? 2 : 1);
     return planes * (size_t)K * round_up(cout + cout_b, 16) * round_up(cin, 32) * sizeof(u16) +
            (mode == ASR_CONV16_F16X2 ? 16 : 0);
 }
@@ -1280,7 +1296,8 @@ int asr_conv16_absmax(asr_hip_context* ctx, const float* x, i64 rows, int c, i64
 int asr_conv16_pack(asr_hip_context* ctx, int mode, const float* wa, const float* wb, int K, int cin, int ca, int cb,
                     void* out) {
     if (!mode_ok(mode))
-        ASR_FAIL(ctx, ASR_HIP_EINVAL, "sparse_conv_pack: mode must be ASR_CONV16_F16, ASR_CONV16_BF16X3 or ASR_CONV16_F16X2");
+        ASR_FAIL(ctx, ASR_HIP_EINVAL,
+                 "sparse_conv_pack: mode must be ASR_CONV16_F16, ASR_CONV16_BF16X3, ASR_CONV16_F16X2 or ASR_CONV16_BF16X3_2ACC");
     if (!wa || !out || K < 1 || K > 56 || cin < 1 || ca < 1 || cb < 0 || (cb > 0 && !wb))
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "sparse_conv_pack: bad argument");
     const int cin_pad = round_up(cin, 32), ctot_pad = round_up(ca + cb, 16);
@@ -1318,7 +1335,7 @@ int asr_conv_sparse16(asr_hip_context* ctx, const asr_sparse_conv_args* pa, cons
     asr_sparse_conv_args a = *pa;
     if (a.num_out <= 0) return ASR_HIP_OK;
     if (!mode_ok(mode)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "sparse_conv16: unknown mode");
-    if (mode != ASR_CONV16_F16 && out_f16) ASR_FAIL(ctx, ASR_HIP_EINVAL, "sparse_conv16: bf16x3 and f16x2 write f32");
+    if (mode != ASR_CONV16_F16 && out_f16) ASR_FAIL(ctx, ASR_HIP_EINVAL, "sparse_conv16: bf16x3, bf16x3_2acc and f16x2 write f32");
     if (a.kernel_size < 1 || a.kernel_size > 56) ASR_FAIL(ctx, ASR_HIP_EINVAL, "sparse_conv16: kernel_size must be 1..56");
     const bool dual = a.cout_b > 0;
     const bool imp = a.inp_importance || a.neighbors_importance;
@@ -1441,6 +1458,11 @@ int asr_conv_sparse16(asr_hip_context* ctx, const asr_sparse_conv_args* pa, cons
                 ASR_L16_SPLIT(8, ASR_CONV16_F16X2)
             else
                 ASR_L16_SPLIT(4, ASR_CONV16_F16X2)
+        } else if (mode == ASR_CONV16_BF16X3_2ACC) {
+            if (nt == 8)
+                ASR_L16_SPLIT(8, ASR_CONV16_BF16X3_2ACC)
+            else
+                ASR_L16_SPLIT(4, ASR_CONV16_BF16X3_2ACC)
         } else {
             if (nt == 8)
                 ASR_L16_SPLIT(8, ASR_CONV16_BF16X3)
@@ -1454,6 +1476,8 @@ int asr_conv_sparse16(asr_hip_context* ctx, const asr_sparse_conv_args* pa, cons
             ASR_L16_NT(32, ASR_CONV16_F16)
     } else if (mode == ASR_CONV16_F16X2) {
         ASR_L16_NT(32, ASR_CONV16_F16X2)
+    } else if (mode == ASR_CONV16_BF16X3_2ACC) {
+        ASR_L16_NT(32, ASR_CONV16_BF16X3_2ACC)
     } else {
         ASR_L16_NT(32, ASR_CONV16_BF16X3)
     }

@@ -342,6 +342,13 @@ int asr_hip_sparse_conv_variant_counts(asr_hip_context* ctx, char* buf, size_t c
  *   Error per product < 2^-21 for elements within 2^-17 of their tensor's maximum, < 2^-38 of the product of the
  *   maxima otherwise.  The activations' scale comes from args->inp_absmax, which the producing convolution keeps
  *   through args->out_absmax (asr_hip_absmax_f32 for other producers).  args as for asr_hip_sparse_conv_f32.
+ * ASR_CONV16_BF16X3_2ACC: bf16x3 with a second accumulator -- the same operands, packed filters (byte for byte) and six
+ *   products, but only the leading product a0*b0 goes to the running sum; the five small ones go to a second f32
+ *   accumulator that is added once, before the epilogue (importance-weighted tiles keep the one chain of bf16x3).
+ *   The running sum is rounded once per step instead of six times: on the full-width network at 1 M points the rms
+ *   error is about 1/3 of the exact-f32 kernel's, with no bias (bf16x3: slightly above it, biased negative), for
+ *   3.5 % more U-Net time than bf16x3 at 10 M points (32 more registers on the 128-column tiles: two blocks per CU
+ *   instead of three).  args as for asr_hip_sparse_conv_f32.
  * All take the filters re-packed by asr_hip_sparse_conv_pack (16-bit, [plane][K][cin panel][cout padded to
  * 16][panel depth] in the kernels' LDS order; bank b appended as columns); args->filters / filters_b are
  * ignored, cout_b > 0 selects the two-bank form.  cin and the row strides must be multiples of 8 (f16) / 4 (f32) elements.
@@ -350,6 +357,7 @@ int asr_hip_sparse_conv_variant_counts(asr_hip_context* ctx, char* buf, size_t c
 #define ASR_CONV16_F16 1
 #define ASR_CONV16_BF16X3 2
 #define ASR_CONV16_F16X2 3
+#define ASR_CONV16_BF16X3_2ACC 4
 size_t asr_hip_sparse_conv_packed_bytes(int mode, int kernel_size, int cin, int cout, int cout_b);
 int asr_hip_sparse_conv_pack(asr_hip_context* ctx, int mode, const float* filters_dev, const float* filters_b_dev,
                              int kernel_size, int cin, int cout, int cout_b, void* packed_out_dev);
@@ -357,6 +365,7 @@ int asr_hip_sparse_conv_f16(asr_hip_context* ctx, const asr_sparse_conv_args* ar
                             int out_is_f16);
 int asr_hip_sparse_conv_bf16x3(asr_hip_context* ctx, const asr_sparse_conv_args* args, const void* packed_dev);
 int asr_hip_sparse_conv_f16x2(asr_hip_context* ctx, const asr_sparse_conv_args* args, const void* packed_dev);
+int asr_hip_sparse_conv_bf16x3_2acc(asr_hip_context* ctx, const asr_sparse_conv_args* args, const void* packed_dev);
 /* f32 bits of the largest |element| of a [rows, cols] matrix with row stride ld (floats) into *out_dev */
 int asr_hip_absmax_f32(asr_hip_context* ctx, const float* x_dev, int64_t rows, int cols, int64_t ld, uint32_t* out_dev);
 /* Row-group plan: the neighbour list re-laid in the order the 16-bit kernels stream it -- per 16 consecutive
@@ -429,7 +438,9 @@ typedef struct asr_implicit_params {
                                  ASR_CONV16_F16 = f16 activations + weights (config C5),
                                  ASR_CONV16_BF16X3 = fp32-class result on the bf16 matrix cores (six MFMAs per
                                  product), ASR_CONV16_F16X2 = fp32-class result on the f16 matrix cores
-                                 (three MFMAs per product, per-tensor power-of-two scaling)             */
+                                 (three MFMAs per product, per-tensor power-of-two scaling),
+                                 ASR_CONV16_BF16X3_2ACC = bf16x3 with a second accumulator for the
+                                 small products (below the exact f32 kernel's error)                    */
 } asr_implicit_params;
 
 /* sizes of the structures built by the last asr_hip_implicit_* call */

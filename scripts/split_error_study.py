@@ -2,11 +2,11 @@
 """Why does bf16x3 carry more error than f16x2 / a plain fp32 sum?  
 
 Runs on the GPU box.  For one cloud (default 1 M points, full width, the bench's weights) the oracle's double-accumulating
-network is the exact result; every arithmetic of the library (f32 MFMA, bf16x3, f16x2) is compared with it: max error / range,
-rms error, share of elements within 1e-5 + 1e-5 |exact|, for `code` and `values`.  `--lib path` loads another build of
-libasr_hip.so (e.g. one compiled with -DASR_BF16X3_CHAIN=1) -- one process per library; the exact result is cached in /tmp.
+network is the exact result; every arithmetic of the library (f32 MFMA, bf16x3, bf16x3_2acc, f16x2) is compared with it: max
+error / range, rms error, mean error / range, share of elements within 1e-5 + 1e-5 |exact|, for `code` and `values`.  `--lib path`
+loads another build of libasr_hip.so -- one process per library; the exact result is cached in /tmp.
 
-usage: python scripts/split_error_study.py [--points N] [--lib build_variants/libasr_hip_chain1.so] [--out gpurun_out/x.json]"""
+usage: python scripts/split_error_study.py [--points N] [--lib path/libasr_hip.so] [--out record.json]"""
 import argparse
 import json
 import os
@@ -28,7 +28,7 @@ def main():
     ap.add_argument("--lib", default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--steps", type=int, default=3, help="timed forwards per arithmetic")
-    ap.add_argument("--time-points", type=int, default=10_000_000, help="U-Net time of bf16x3 on a cloud of this size (0: skip)")
+    ap.add_argument("--time-points", type=int, default=10_000_000, help="U-Net time of bf16x3 and bf16x3_2acc on a cloud of this size (0: skip)")
     args = ap.parse_args()
     from asr_hip import _lib
     if args.lib:
@@ -67,7 +67,7 @@ def main():
 
     rec = {"points": n, "lib": args.lib or "default", "arithmetic": {}}
     rec["arithmetic"]["fp32 CPU oracle"] = {k: stats(ref32[k], k) for k in ("code", "values")}
-    for precision in ("f32", "bf16x3", "f16x2"):
+    for precision in ("f32", "bf16x3", "bf16x3_2acc", "f16x2"):
         pipe = ImplicitPipeline(weights, device=gpu, precision=precision)
         values = pipe.forward(pts, nrm, radii, bb[0], bb[1])
         r = {"code": stats(pipe.get("code").cpu().numpy(), "code"), "values": stats(values.cpu().numpy(), "values")}
@@ -85,12 +85,14 @@ def main():
         pts, nrm = synth.scan_cloud(args.time_points, seed=1000, device=gpu)
         radii = synth.knn_radii_gpu(pts, 24)
         bb = synth.bounding_box(pts, 0.1)
-        pipe = ImplicitPipeline(weights, device=gpu, precision="bf16x3")
-        ms = []
-        for _ in range(2 + args.steps):
-            pipe.forward(pts, nrm, radii, bb[0], bb[1])
-            ms.append(pipe.stage_ms()["unet"])
-        rec["bf16x3_unet_ms_at_%d" % args.time_points] = min(ms[2:])
+        for precision in ("bf16x3", "bf16x3_2acc"):
+            pipe = ImplicitPipeline(weights, device=gpu, precision=precision)
+            ms = []
+            for _ in range(2 + args.steps):
+                pipe.forward(pts, nrm, radii, bb[0], bb[1])
+                ms.append(pipe.stage_ms()["unet"])
+            rec["%s_unet_ms_at_%d" % (precision, args.time_points)] = min(ms[2:])
+            del pipe
     print(json.dumps(rec, indent=1))
     if args.out:
         with open(args.out, "w") as f:
