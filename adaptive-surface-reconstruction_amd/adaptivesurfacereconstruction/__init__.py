@@ -176,13 +176,15 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
                         density_percentile_threshold=10.0, point_radius_estimation_knn=24,
                         octree_max_depth=21, contouring_value_threshold=1.0,
                         keep_n_connected_components=2**63 - 1, minimum_component_size=3, *, weights=None,
-                        precision="f32"):
+                        precision="f32", vertex_normals=False):
     """module.cpp:58-109,291-346 -> asr::ReconstructSurface (cpp/lib/asr.cpp:95-349): pre-filter,
     implicit values, dual contouring, component filter; every stage on the MI355X.
     `weights` (keyword only) replaces the reference's bundled model.pt, see _load_weights.
     `precision` (keyword only): arithmetic of the network's sparse convolutions, one of asr_hip._lib.PRECISIONS --
     "f32" (default, the reference's arithmetic), "bf16x3_2acc" (bf16 matrix cores, a third of the f32 arithmetic's
-    rms error, half its U-Net time), "bf16x3", "f16x2" or "f16" (see asr_hip.pipeline.ImplicitPipeline)."""
+    rms error, half its U-Net time), "bf16x3", "f16x2" or "f16" (see asr_hip.pipeline.ImplicitPipeline).
+    `vertex_normals` (keyword only): the result also holds "vertex_normals" f32 [V,3], the unit gradient of the
+    network's field at every final vertex (ImplicitPipeline.query), zero where the gradient vanishes."""
     from asr_hip.pipeline import ImplicitPipeline
     if precision not in _lib.PRECISIONS:
         raise ValueError("precision must be one of %s" % ", ".join(sorted(_lib.PRECISIONS)))
@@ -219,7 +221,19 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
     pipe.forward(torch.from_numpy(points).to(dev), torch.from_numpy(normals).to(dev),
                  torch.from_numpy(radii).to(dev), bb_min, bb_max)
     v, t = pipe.mesh(contouring_value_threshold, keep_n_connected_components, minimum_component_size)
-    return {"vertices": v.cpu().numpy(), "triangles": t.cpu().numpy()}
+    result = {"vertices": v.cpu().numpy(), "triangles": t.cpu().numpy()}
+    if vertex_normals:
+        _, grad = pipe.query(v, gradient=True)
+        result["vertex_normals"] = _unit_normals(grad.cpu().numpy())
+    return result
+
+
+def _unit_normals(grad):
+    """grad / |grad| per row as f32 [V,3]; zero rows where |grad| is 0 (or not finite)"""
+    grad = np.asarray(grad, np.float32).reshape(-1, 3)
+    norm = np.sqrt((grad * grad).sum(1, keepdims=True))
+    ok = np.isfinite(norm) & (norm > 0)
+    return np.where(ok, grad / np.where(ok, norm, np.float32(1)), np.float32(0)).astype(np.float32)
 
 
 def remove_connected_components(vertices, triangles, keep_n_largest_components,

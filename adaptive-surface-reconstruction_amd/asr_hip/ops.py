@@ -585,6 +585,46 @@ def decode_mlp(code, w1, b1, w2, b2, w3, voxel_sizes=None):
     return out
 
 
+def leaf_locate(frame, leaf_keys, positions):
+    """row of the leaf of `leaf_keys` (sorted ascending, tiling the root cube of `frame`) that contains each position,
+    -1 outside the cube or for non-finite positions (asr_hip_leaf_locate) -> int32 [M]"""
+    leaf_keys = _dev(leaf_keys, torch.int64)  # uint64 bit patterns
+    positions = _dev(positions, torch.float32)
+    if positions.ndim != 2 or positions.shape[1] != 3:
+        raise ValueError("positions must have shape [M,3]")
+    rows = torch.empty(positions.shape[0], dtype=torch.int32, device=positions.device)
+    context(_same_device(leaf_keys, positions)).call("asr_hip_leaf_locate", ctypes.byref(frame), ptr(leaf_keys),
+                                                     i64(leaf_keys.numel()), ptr(positions), i64(positions.shape[0]),
+                                                     ptr(rows))
+    return rows
+
+
+def decode_mlp_at(code, shifts, w1, b1, w2, b2, w3, rows=None, voxel_sizes=None, gradient=False):
+    """UNet5.decode(shifts, code[rows]) (net_definitions_torch.py:655-666) -> values [M,2]; with gradient=True
+    (values, grad [M,3]) where grad is decode_with_gradient's d values[:,0] / d shift (:668-686, unscaled).
+    rows (int32 [M], None: row i) picks the code row of each shift, a row < 0 gives NaN; voxel_sizes (indexed by row)
+    multiplies values[:,0] (sdf scale)."""
+    code = _dev(code, torch.float32)
+    shifts = _dev(shifts, torch.float32)
+    w1, b1, w2, b2, w3 = (_dev(t, torch.float32) for t in (w1, b1, w2, b2, w3))
+    rows = _dev(rows, torch.int32) if rows is not None else None
+    sizes = _dev(voxel_sizes, torch.float32) if voxel_sizes is not None else None
+    if shifts.ndim != 2 or shifts.shape[1] != 3:
+        raise ValueError("shifts must have shape [M,3]")
+    m = shifts.shape[0]
+    if rows is None and code.shape[0] != m:
+        raise ValueError("without rows, code and shifts need the same number of rows")
+    if rows is not None and tuple(rows.shape) != (m,):
+        raise ValueError("rows must have shape [M]")
+    values = torch.empty((m, 2), dtype=torch.float32, device=shifts.device)
+    grad = torch.empty((m, 3), dtype=torch.float32, device=shifts.device) if gradient else None
+    dev = _same_device(code, shifts, w1, b1, w2, b2, w3, rows, sizes)
+    context(dev).call("asr_hip_decode_mlp_at", ptr(code), int(code.shape[1]), ptr(rows), ptr(shifts), i64(m),
+                      ptr(w1), ptr(b1), int(w1.shape[0]), ptr(w2), ptr(b2), int(w2.shape[0]), ptr(w3), ptr(sizes),
+                      ptr(values), ptr(grad))
+    return (values, grad) if gradient else values
+
+
 def density_inlier(counts, density_percentile_threshold):
     """asr::ComputeInlierFromDensity (cpp/lib/preprocess.cpp:41-62) on host counts, literally
     (see asr_density_inlier in include/asr_hip.h)"""

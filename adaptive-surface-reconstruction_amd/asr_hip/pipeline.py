@@ -179,6 +179,26 @@ class ImplicitPipeline:
                       self._table, len(self._weights), ctypes.byref(p))
         return self.get("feats1"), self.get("importance")
 
+    def query(self, positions, gradient=False, return_rows=False):
+        """The implicit field of the last forward at arbitrary positions [M,3] (asr_hip_implicit_query): values [M,2]
+        as the forward computes them at the voxel centres (values[:,0] scaled by the voxel size when scale_sdf),
+        NaN outside the octree.  gradient=True adds d values[:,0] / d position [M,3]; return_rows=True adds the
+        grid-0 row of every position (-1 outside).  Returns values, or a tuple (values[, grad][, rows])."""
+        if not isinstance(positions, torch.Tensor):
+            positions = torch.from_numpy(np.ascontiguousarray(positions, dtype=np.float32))
+        positions = positions.to(self.device, torch.float32).contiguous()
+        if positions.ndim != 2 or positions.shape[1] != 3:
+            raise ValueError("positions must have shape [M,3]")
+        self._stream()
+        m = positions.shape[0]
+        values = torch.empty((m, 2), dtype=torch.float32, device=self.device)
+        grad = torch.empty((m, 3), dtype=torch.float32, device=self.device) if gradient else None
+        rows = torch.empty(m, dtype=torch.int32, device=self.device) if return_rows else None
+        self.ctx.call("asr_hip_implicit_query", ptr(positions), ctypes.c_int64(m), self._table, len(self._weights),
+                      ptr(values), ptr(grad), ptr(rows))
+        out = (values,) + ((grad,) if gradient else ()) + ((rows,) if return_rows else ())
+        return out if len(out) > 1 else values
+
     def get(self, name):
         """copy of one named array of the last forward (see include/asr_hip.h)"""
         base = name if name in _ARRAY_TYPES else name.rstrip("0123456789")

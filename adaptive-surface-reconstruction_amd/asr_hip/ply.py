@@ -92,14 +92,22 @@ def write_points(path, points, normals, radii=None, binary=True):
             np.savetxt(f, table, fmt="%.9g")
 
 
-def write_mesh(path, vertices, triangles, binary=True):
-    """triangle mesh: vertices f32[M,3], triangles i32[T,3] (the result dict of reconstruct_surface)"""
+def write_mesh(path, vertices, triangles, binary=True, normals=None):
+    """triangle mesh: vertices f32[M,3], triangles i32[T,3] (the result dict of reconstruct_surface); normals
+    f32[M,3] (optional) become the vertex properties nx ny nz"""
     v = np.asarray(vertices, np.float32).reshape(-1, 3)
     t = np.asarray(triangles, np.int32).reshape(-1, 3)
+    nprops = ""
+    if normals is not None:
+        nrm = np.asarray(normals, np.float32).reshape(-1, 3)
+        if len(nrm) != len(v):
+            raise ValueError("normals must have one row per vertex")
+        v = np.concatenate([v, nrm], 1)
+        nprops = "property float nx\nproperty float ny\nproperty float nz\n"
     with open(path, "wb") as f:
-        f.write(("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+        f.write(("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
                  "element face %d\nproperty list uchar int vertex_indices\nend_header\n"
-                 % ("binary_little_endian" if binary else "ascii", len(v), len(t))).encode())
+                 % ("binary_little_endian" if binary else "ascii", len(v), nprops, len(t))).encode())
         if binary:
             f.write(v.astype("<f4").tobytes())
             rec = np.empty(len(t), dtype=[("n", "u1"), ("i", "<i4", 3)])
@@ -111,8 +119,9 @@ def write_mesh(path, vertices, triangles, binary=True):
             np.savetxt(f, np.concatenate([np.full((len(t), 1), 3), t], 1), fmt="%d")
 
 
-def read_mesh(path):
-    """inverse of write_mesh (tests)"""
+def read_mesh(path, with_normals=False):
+    """inverse of write_mesh (tests): (vertices, triangles), or (vertices, triangles, normals or None) with
+    with_normals=True"""
     with open(path, "rb") as f:
         header = []
         while True:
@@ -122,11 +131,15 @@ def read_mesh(path):
                 break
         nv = int([h for h in header if h.startswith("element vertex")][0].split()[2])
         nt = int([h for h in header if h.startswith("element face")][0].split()[2])
+        cols = 6 if "property float nx" in header else 3
         if "format ascii 1.0" in header:
-            v = np.loadtxt(f, dtype=np.float32, max_rows=nv, ndmin=2).reshape(-1, 3)
+            v = np.loadtxt(f, dtype=np.float32, max_rows=nv, ndmin=2).reshape(-1, cols)
             t = np.loadtxt(f, dtype=np.int32, max_rows=nt, ndmin=2).reshape(-1, 4)[:, 1:] if nt else np.zeros((0, 3), np.int32)
         else:
-            v = np.frombuffer(f.read(12 * nv), "<f4").reshape(-1, 3)
+            v = np.frombuffer(f.read(4 * cols * nv), "<f4").reshape(-1, cols)
             rec = np.frombuffer(f.read(13 * nt), dtype=[("n", "u1"), ("i", "<i4", 3)])
             t = rec["i"].astype(np.int32)
-    return v.astype(np.float32), t
+    v = v.astype(np.float32)
+    if with_normals:
+        return np.ascontiguousarray(v[:, :3]), t, (np.ascontiguousarray(v[:, 3:]) if cols == 6 else None)
+    return np.ascontiguousarray(v[:, :3]), t

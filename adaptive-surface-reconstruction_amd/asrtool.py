@@ -20,6 +20,7 @@ Arguments:
 Options:
     --weights FILE  Network weights (TorchScript model.pt, state dict .pt or .npz); default $ASR_RESOURCE_DIR
     --precision NAME  Arithmetic of the network's sparse convolutions: f32 (default), bf16x3_2acc, bf16x3, f16x2, f16
+    --normals  Writes per-vertex normals (nx ny nz): the unit gradient of the network's field at each vertex
     --version  Prints the version information
     --third-party-notices  Prints third-party software notices
 """
@@ -59,8 +60,9 @@ def main(argv=None):
     print("reading points")
     points, normals, radii = ply.read_points(inp)
     print("%d / %d" % (len(points), len(points)))
-    result = asr.reconstruct_surface(points, normals, radii, weights=_option(argv, "--weights"), precision=precision)
-    ply.write_mesh(out, result["vertices"], result["triangles"])
+    result = asr.reconstruct_surface(points, normals, radii, weights=_option(argv, "--weights"), precision=precision,
+                                     vertex_normals="--normals" in argv)
+    ply.write_mesh(out, result["vertices"], result["triangles"], normals=result.get("vertex_normals"))
     print("wrote %s: %d vertices, %d triangles" % (out, len(result["vertices"]), len(result["triangles"])))
     return 0
 

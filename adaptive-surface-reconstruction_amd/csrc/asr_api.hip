@@ -652,6 +652,23 @@ int asr_hip_decode_mlp(asr_hip_context* ctx, const float* code, int64_t v, int c
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "decode_mlp: null argument");
     return asr_conv_decode(ctx, code, v, c, w1, b1, h1, w2, b2, h2, w3, sizes, out);
 }
+int asr_hip_leaf_locate(asr_hip_context* ctx, const asr_octree_frame* frame, const uint64_t* leaf_keys, int64_t num_leaves,
+                        const float* positions, int64_t m, int32_t* rows_out) {
+    CTX_GUARD(ctx);
+    if (m < 0 || num_leaves < 0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "leaf_locate: negative size");
+    if (m > 0 && (!frame || !positions || !rows_out || (num_leaves > 0 && !leaf_keys)))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "leaf_locate: null argument");
+    return asr_query_leaf_locate(ctx, frame, leaf_keys, num_leaves, positions, m, rows_out);
+}
+int asr_hip_decode_mlp_at(asr_hip_context* ctx, const float* code, int c, const int32_t* rows, const float* shifts,
+                          int64_t m, const float* w1, const float* b1, int h1, const float* w2, const float* b2, int h2,
+                          const float* w3, const float* sizes, float* values_out, float* grad_out) {
+    CTX_GUARD(ctx);
+    if (m < 0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "decode_mlp_at: negative size");
+    if (m > 0 && (!code || !shifts || !w1 || !b1 || !w2 || !b2 || !w3 || !values_out))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "decode_mlp_at: null argument");
+    return asr_query_decode_at(ctx, code, c, rows, shifts, m, w1, b1, h1, w2, b2, h2, w3, sizes, values_out, grad_out);
+}
 
 }  // extern "C"
 
@@ -1059,6 +1076,7 @@ int build_begin(asr_hip_context* ctx, i64 n, const asr_implicit_params* prm) {
     ctx->scratch.reset();
     ctx->named.clear();
     ctx->values = ctx->feats1 = ctx->importance = ctx->code = nullptr;
+    ctx->code_ok = false;
     ctx->agg_rs = nullptr;
     ctx->agg_idx = ctx->agg_spos = nullptr;
     ctx->agg_dist = ctx->agg_compat = nullptr;
@@ -1384,6 +1402,7 @@ int implicit_aggregate(asr_hip_context* ctx, const float* points, const float* n
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "implicit_network: no matching implicit_build");
     if (!ctx->has_search || !ctx->agg_rs || !ctx->agg_sorted)  // what the LAST BUILD did, not the option's value now
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "implicit_network: the build skipped the aggregation search (option build_search)");
+    ctx->code_ok = false;  // the arena rewind below gives up the last forward's `code`
     ctx->scratch.reset();
     if (ctx->build_mark_ok) arena_rewind(ctx->persist, ctx->build_mark);
     if (net.precision != 0 && net.precision != ASR_CONV16_F16 && net.precision != ASR_CONV16_BF16X3 &&
@@ -1572,6 +1591,10 @@ int network_unet_decode(asr_hip_context* ctx, Net& net, const asr_implicit_param
     ctx->values = values;
     name_it(ctx, "values", values, 8 * (size_t)V0);
     ASR_HIP_CHECK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
+    // asr_hip_implicit_query: a sharded forward's `code` holds the owned rows only
+    ctx->code_ok = !ctx->dry_launch && !(ctx->shard && asr_shard_world(ctx->shard) > 1);
+    ctx->code_width = c_dec[0];
+    ctx->code_scale_sdf = prm->scale_sdf ? 1 : 0;
     return ASR_HIP_OK;
 }
 
@@ -1708,6 +1731,33 @@ int asr_hip_implicit_forward_sharded(asr_hip_context* ctx, const asr_shard_comm*
     if (stats) *stats = *asr_shard_get_stats(st);
     asr_shard_free(st);
     return rc;
+}
+int asr_hip_implicit_query(asr_hip_context* ctx, const float* positions, int64_t m, const asr_weight* weights,
+                           int num_weights, float* values_out, float* grad_out, int32_t* rows_out) {
+    CTX_GUARD(ctx);
+    if (m < 0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "implicit_query: negative size");
+    if (!ctx->code_ok || !ctx->code)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "implicit_query: no complete network output -- run asr_hip_implicit_forward (or "
+                                      "asr_hip_implicit_network after asr_hip_implicit_build) first; a failed forward, a build "
+                                      "alone and a forward sharded over several ranks leave none");
+    if (m == 0) return ASR_HIP_OK;
+    if (!positions || !values_out || (num_weights > 0 && !weights))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "implicit_query: null argument");
+    Net net{ctx, {weights, num_weights}};
+    const asr_weight *w1, *b1, *w2, *b2, *w3;
+    ASR_TRY(net.get("dense_decoder1.weight", 2, &w1));
+    ASR_TRY(net.get("dense_decoder1.bias", 1, &b1));
+    ASR_TRY(net.get("dense_decoder2.weight", 2, &w2));
+    ASR_TRY(net.get("dense_decoder2.bias", 1, &b2));
+    ASR_TRY(net.get("dense_decoder3.weight", 2, &w3));
+    if (w1->shape[1] != 3 + ctx->code_width || w2->shape[1] != w1->shape[0] || w3->shape[1] != w2->shape[0] ||
+        w3->shape[0] != 2 || b1->shape[0] != w1->shape[0] || b2->shape[0] != w2->shape[0])
+        ASR_FAIL(ctx, ASR_HIP_EWEIGHT, "dense_decoder shapes do not chain with the last forward's code width %d",
+                 ctx->code_width);
+    const GridDev& g0 = ctx->grids[0];
+    return asr_query_implicit(ctx, &ctx->frame, g0.keys, g0.centers, g0.sizes, g0.v, ctx->code, ctx->code_width,
+                              w1->data, b1->data, (int)w1->shape[0], w2->data, b2->data, (int)w2->shape[0], w3->data,
+                              ctx->code_scale_sdf, positions, m, values_out, grad_out, rows_out);
 }
 int asr_hip_implicit_get(asr_hip_context* ctx, const char* name, void* dst, size_t* nbytes) {
     CTX_GUARD(ctx);

@@ -219,6 +219,11 @@ struct asr_hip_context {
     int feats1_width = 0;
     float* importance = nullptr;
     float* code = nullptr;
+    // asr_hip_implicit_query: `code` holds every grid-0 row of the last forward (false after a build alone, a failed or a
+    // sharded forward), code_width its columns, code_scale_sdf that forward's scale_sdf
+    bool code_ok = false;
+    int code_width = 0;
+    int code_scale_sdf = 0;
     float stage_ms[6] = {0, 0, 0, 0, 0, 0};
     hipEvent_t ev[8] = {};
     bool ev_ok = false;
@@ -336,6 +341,36 @@ __device__ static inline void asr_key_coord(u64 key, int& x, int& y, int& z, int
     x = (int)asr_compact21(k);
     y = (int)asr_compact21(k >> 1);
     z = (int)asr_compact21(k >> 2);
+}
+
+// point -> integer cell of `level` in the frame (octree.h:49-66, Octree::ComputeCoord).  Translation units that use it
+// are compiled with -ffp-contract=off (csrc/Makefile GEOM_FLAGS), so that every caller rounds like the reference.
+__device__ static inline void frame_coord(const asr_octree_frame& f, float px, float py, float pz,
+                                          int level, int& x, int& y, int& z) {
+    float inv = f.inv_voxel_size[ASR_MAX_LEVEL];
+    float tx = px * inv, ty = py * inv, tz = pz * inv;
+    x = (int)floorf(tx) + f.offset[0];
+    y = (int)floorf(ty) + f.offset[1];
+    z = (int)floorf(tz) + f.offset[2];
+    int s = ASR_MAX_LEVEL - level;
+    x >>= s;
+    y >>= s;
+    z >>= s;
+}
+// frame_coord at level 21 for an arbitrary point: false (and no int conversion) unless all three cells lie in
+// [0, 2^21) -- non-finite and huge inputs are rejected by the float comparisons.  Equal to frame_coord where true.
+__device__ static inline bool frame_coord21_checked(const asr_octree_frame& f, float px, float py, float pz, int& x,
+                                                    int& y, int& z) {
+    float inv = f.inv_voxel_size[ASR_MAX_LEVEL];
+    float tx = floorf(px * inv), ty = floorf(py * inv), tz = floorf(pz * inv);
+    const float lim = (float)(1 << ASR_MAX_LEVEL);
+    if (!(tx >= (float)-f.offset[0] && tx < lim - (float)f.offset[0] && ty >= (float)-f.offset[1] &&
+          ty < lim - (float)f.offset[1] && tz >= (float)-f.offset[2] && tz < lim - (float)f.offset[2]))
+        return false;
+    x = (int)tx + f.offset[0];
+    y = (int)ty + f.offset[1];
+    z = (int)tz + f.offset[2];
+    return true;
 }
 
 // 64-bit finaliser (murmur3 fmix64) used by all device hash tables
@@ -496,3 +531,14 @@ int asr_conv_reduce(asr_hip_context* ctx, const float* values, const int32_t* gi
 int asr_conv_decode(asr_hip_context* ctx, const float* code, i64 v, int c, const float* w1,
                     const float* b1, int h1, const float* w2, const float* b2, int h2,
                     const float* w3, const float* sizes, float* out, const int32_t* rows = nullptr);  // rows: v listed rows
+// asr_query.hip: leaf location, decoder at shifts (sizes: values[:, 0] *= sizes[row]; grad = d decode[:, 0] / d shift),
+// and the fused whole-path query on a leaf set with its centres and sizes
+int asr_query_leaf_locate(asr_hip_context* ctx, const asr_octree_frame* frame, const u64* keys, i64 n, const float* pos,
+                          i64 m, int32_t* rows);
+int asr_query_decode_at(asr_hip_context* ctx, const float* code, int c, const int32_t* rows, const float* shifts, i64 m,
+                        const float* w1, const float* b1, int h1, const float* w2, const float* b2, int h2,
+                        const float* w3, const float* sizes, float* values, float* grad);
+int asr_query_implicit(asr_hip_context* ctx, const asr_octree_frame* frame, const u64* keys, const float* centers,
+                       const float* sizes, i64 num_leaves, const float* code, int c, const float* w1, const float* b1,
+                       int h1, const float* w2, const float* b2, int h2, const float* w3, int scale_sdf,
+                       const float* pos, i64 m, float* values, float* grad, int32_t* rows_out);

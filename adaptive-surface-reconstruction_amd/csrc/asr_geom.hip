@@ -154,18 +154,6 @@ __device__ inline int level_from_scale(const asr_octree_frame& f, float scale) {
         if (f.voxel_size[level] < scale) return level - 1 > 0 ? level - 1 : 0;
     return ASR_MAX_LEVEL;
 }
-__device__ inline void frame_coord(const asr_octree_frame& f, float px, float py, float pz,
-                                   int level, int& x, int& y, int& z) {
-    float inv = f.inv_voxel_size[ASR_MAX_LEVEL];
-    float tx = px * inv, ty = py * inv, tz = pz * inv;
-    x = (int)floorf(tx) + f.offset[0];
-    y = (int)floorf(ty) + f.offset[1];
-    z = (int)floorf(tz) + f.offset[2];
-    int s = ASR_MAX_LEVEL - level;
-    x >>= s;
-    y >>= s;
-    z >>= s;
-}
 __device__ inline u64 point_key(const asr_octree_frame& f, const float* pts, const float* radii,
                                 i64 i, float radius_scale, int max_depth) {
     float px = pts[3 * i], py = pts[3 * i + 1], pz = pts[3 * i + 2];

@@ -419,6 +419,25 @@ int asr_hip_decode_mlp(asr_hip_context* ctx, const float* code_dev, int64_t v, i
                        const float* b2_dev, int h2, const float* w3_dev,
                        const float* sizes_dev, float* out_dev);
 
+/* ---- the implicit field at arbitrary points: UNet5.decode / decode_with_gradient at shifts
+ *      (net_definitions_torch.py:655-686) ------------------------------------------------------- */
+/* Row of the leaf that contains each position: leaf_keys_dev [num_leaves] sorted ascending, a leaf set that tiles the
+ * root cube (grid 0 of a build, the leaves of asr_hip_octree_get).  The frame's key convention (asr_hip_point_keys):
+ * c = floor(p * inv_voxel_size[21]) + offset per axis; a position is inside when all three c lie in [0, 2^21), and its
+ * row is that of the leaf whose key is the key of (c >> (21 - l), l) at that leaf's level l.  Non-finite positions and
+ * positions outside the cube get -1.  Memory-safe on any input; every row lies in [-1, num_leaves). */
+int asr_hip_leaf_locate(asr_hip_context* ctx, const asr_octree_frame* frame, const uint64_t* leaf_keys_dev,
+                        int64_t num_leaves, const float* positions_dev, int64_t m, int32_t* rows_out_dev);
+/* decode at given shifts: values_out[i] = decode(shifts[i], code[rows[i]]) for the layer order
+ * [s | code] -> h1 -> ReLU -> h2 -> ReLU -> 2 (weights as asr_hip_decode_mlp).  rows_dev NULL: row i; a row < 0 gives
+ * NaN.  shifts_dev [m,3], any values.  sizes_dev (NULL: none): values_out[i,0] *= sizes[row].  grad_out_dev [m,3]
+ * (NULL: not computed): decode_with_gradient's z1[:, :3] = d decode[:,0] / d shift (unscaled). */
+int asr_hip_decode_mlp_at(asr_hip_context* ctx, const float* code_dev, int c, const int32_t* rows_dev,
+                          const float* shifts_dev, int64_t m, const float* w1_dev, const float* b1_dev, int h1,
+                          const float* w2_dev, const float* b2_dev, int h2, const float* w3_dev, const float* sizes_dev,
+                          float* values_out_dev, float* grad_out_dev);
+/* (asr_hip_implicit_query, the whole-path query on the last forward, is declared after asr_hip_implicit_stage_ms) */
+
 /* ---- whole path: the section of asr::ReconstructSurface between the pre-filter and the
  *      contouring (cpp/lib/asr.cpp:143-336) ---------------------------------------------- */
 typedef struct asr_weight {
@@ -548,6 +567,16 @@ int asr_hip_implicit_get(asr_hip_context* ctx, const char* name, void* dst_dev,
  * joined), [7] network wall.  With option "overlap" (default) the search runs on a second stream
  * concurrently with the grids: [2] is measured on that stream and [0]+[1]+[2] exceeds [6]. */
 int asr_hip_implicit_stage_ms(asr_hip_context* ctx, float out_ms[8]);
+/* The field of the last forward at positions_dev [m,3]: row = asr_hip_leaf_locate on grid 0 of that forward's frame,
+ * s = (p - centre[row]) / size[row], values_out [m,2] = decode(s, code[row]) with values[:,0] *= size[row] when that
+ * forward had scale_sdf; grad_out [m,3] (NULL: not computed) = d values[:,0] / d p inside the leaf (ReLU derivative 0
+ * at 0).  Outside positions: NaN values and gradient, row -1.  rows_out [m] (NULL: not written).  The decoder weights
+ * are looked up by name as in the forward.  Asynchronous on the context's stream; no device memory beyond the
+ * caller's buffers.  At the centres of grid 0 the values are the forward's bits (released widths).  ASR_HIP_EINVAL
+ * before a forward, after a build alone, after a failed forward and after a forward sharded over several ranks;
+ * m = 0 is a no-op. */
+int asr_hip_implicit_query(asr_hip_context* ctx, const float* positions_dev, int64_t m, const asr_weight* weights,
+                           int num_weights, float* values_out_dev, float* grad_out_dev, int32_t* rows_out_dev);
 
 #ifdef __cplusplus
 }
