@@ -176,7 +176,7 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
                         density_percentile_threshold=10.0, point_radius_estimation_knn=24,
                         octree_max_depth=21, contouring_value_threshold=1.0,
                         keep_n_connected_components=2**63 - 1, minimum_component_size=3, *, weights=None,
-                        precision="f32", vertex_normals=False):
+                        precision="f32", vertex_normals=False, point_attributes=None):
     """module.cpp:58-109,291-346 -> asr::ReconstructSurface (cpp/lib/asr.cpp:95-349): pre-filter,
     implicit values, dual contouring, component filter; every stage on the MI355X.
     `weights` (keyword only) replaces the reference's bundled model.pt, see _load_weights.
@@ -184,7 +184,10 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
     "f32" (default, the reference's arithmetic), "bf16x3_2acc" (bf16 matrix cores, a third of the f32 arithmetic's
     rms error, half its U-Net time), "bf16x3", "f16x2" or "f16" (see asr_hip.pipeline.ImplicitPipeline).
     `vertex_normals` (keyword only): the result also holds "vertex_normals" f32 [V,3], the unit gradient of the
-    network's field at every final vertex (ImplicitPipeline.query), zero where the gradient vanishes."""
+    network's field at every final vertex (ImplicitPipeline.query), zero where the gradient vanishes.
+    `point_attributes` (keyword only): f32-convertible [num_points] or [num_points, C], e.g. the colours of the scan;
+    the result then holds "vertex_attributes" f32 [V,C], the attributes of the inlier points blended at every final
+    vertex at the scale of the leaf that contains it (ImplicitPipeline.transfer), 0 where no point is near."""
     from asr_hip.pipeline import ImplicitPipeline
     if precision not in _lib.PRECISIONS:
         raise ValueError("precision must be one of %s" % ", ".join(sorted(_lib.PRECISIONS)))
@@ -195,6 +198,15 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
         raise ValueError("normals must have shape [num_points,3]")
     if radii.ndim != 1 or radii.shape[0] not in (0, points.shape[0]):
         raise ValueError("radii must have shape [num_point3]")
+    if point_attributes is not None:
+        try:
+            point_attributes = np.ascontiguousarray(point_attributes, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("point_attributes must be convertible to float32") from None
+        if point_attributes.ndim == 1:
+            point_attributes = point_attributes[:, None]
+        if point_attributes.ndim != 2 or point_attributes.shape[0] != points.shape[0] or point_attributes.shape[1] < 1:
+            raise ValueError("point_attributes must have shape [num_points] or [num_points, C]")
     if points.shape[0] == 0:
         raise RuntimeError("points is null!\n")
     # preprocess (asr.cpp:116-135)
@@ -210,6 +222,8 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
         radii = r.cpu().numpy()
         inlier = inl.cpu().numpy().astype(bool)
     points, normals, radii = points[inlier], normals[inlier], radii[inlier]
+    if point_attributes is not None:
+        point_attributes = np.ascontiguousarray(point_attributes[inlier])
     if points.shape[0] == 0:
         raise RuntimeError("no points left after the pre-filter")
     dev = torch.device("cuda")
@@ -218,13 +232,16 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
                             scale_sdf=True, precision=precision)
     # exact bounding box of the filtered points (asr.cpp:148-150; quirk B.1 applies)
     bb_min, bb_max = points.min(0), points.max(0)
-    pipe.forward(torch.from_numpy(points).to(dev), torch.from_numpy(normals).to(dev),
-                 torch.from_numpy(radii).to(dev), bb_min, bb_max)
+    points_dev, radii_dev = torch.from_numpy(points).to(dev), torch.from_numpy(radii).to(dev)
+    pipe.forward(points_dev, torch.from_numpy(normals).to(dev), radii_dev, bb_min, bb_max)
     v, t = pipe.mesh(contouring_value_threshold, keep_n_connected_components, minimum_component_size)
     result = {"vertices": v.cpu().numpy(), "triangles": t.cpu().numpy()}
     if vertex_normals:
         _, grad = pipe.query(v, gradient=True)
         result["vertex_normals"] = _unit_normals(grad.cpu().numpy())
+    if point_attributes is not None:
+        result["vertex_attributes"] = pipe.transfer(points_dev, radii_dev, torch.from_numpy(point_attributes).to(dev),
+                                                    v).cpu().numpy()
     return result
 
 

@@ -151,6 +151,7 @@ EXPORTS = [
     "asr_hip_multi_radius_search_fill", "asr_hip_knn_radius", "asr_hip_radius_neighbor_count", "asr_hip_continuous_conv_f32", "asr_hip_continuous_conv_basis_f32",
     "asr_hip_aggregation_importance", "asr_hip_sparse_conv_f32", "asr_hip_invert_neighbors_list", "asr_hip_row_groups",
     "asr_hip_reduce_subarrays_sum", "asr_hip_decode_mlp", "asr_hip_leaf_locate", "asr_hip_decode_mlp_at",
+    "asr_hip_point_attributes_at",
     "asr_hip_implicit_build",
     "asr_hip_implicit_network", "asr_hip_implicit_aggregate", "asr_hip_implicit_forward", "asr_hip_implicit_get",
     "asr_hip_implicit_stage_ms", "asr_hip_implicit_query",

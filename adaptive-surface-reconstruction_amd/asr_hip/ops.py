@@ -599,6 +599,43 @@ def leaf_locate(frame, leaf_keys, positions):
     return rows
 
 
+def point_attributes_at(frame, points, radii, attributes, positions, sizes, max_widen=3, min_weight=1e-2, fill=0.0,
+                        return_info=False):
+    """Per-point attributes [N,C] (or [N]: one channel) blended at positions [M,3] with the aggregation's own weight
+    (asr_hip_point_attributes_at): for k = 0..max_widen and R = sizes[j] * 2**k, the points with squared distance
+    < R*R weigh (min(R, 2r)/max(R, 2r))**2 * clamp((1 - d/R**2)**3, 0, 1); row j is their weighted mean for the first
+    k whose weight sum reaches min_weight.  Rows without such a k, positions outside the frame's cube or non-finite,
+    and sizes that are not finite and > 0 get `fill`.  -> f32 [M,C]; return_info=True adds (weight f32 [M], the chosen
+    weight sum or 0, and widen int8 [M], the chosen k or -1)."""
+    points = _dev(points, torch.float32)
+    radii = _dev(radii, torch.float32)
+    attributes = _dev(attributes, torch.float32)
+    positions = _dev(positions, torch.float32)
+    sizes = _dev(sizes, torch.float32)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError("points must have shape [N,3]")
+    n = points.shape[0]
+    if attributes.ndim == 1:
+        attributes = attributes[:, None].contiguous()
+    if tuple(radii.shape) != (n,):
+        raise ValueError("radii must have shape [N]")
+    if attributes.ndim != 2 or attributes.shape[0] != n:
+        raise ValueError("attributes must have shape [N] or [N,C]")
+    if positions.ndim != 2 or positions.shape[1] != 3:
+        raise ValueError("positions must have shape [M,3]")
+    m, c = positions.shape[0], attributes.shape[1]
+    if tuple(sizes.shape) != (m,):
+        raise ValueError("sizes must have shape [M]")
+    out = torch.empty((m, c), dtype=torch.float32, device=points.device)
+    weight = torch.empty(m, dtype=torch.float32, device=points.device) if return_info else None
+    widen = torch.empty(m, dtype=torch.int8, device=points.device) if return_info else None
+    context(_same_device(points, radii, attributes, positions, sizes)).call(
+        "asr_hip_point_attributes_at", ctypes.byref(frame), ptr(points), ptr(radii), i64(n), ptr(attributes), int(c),
+        ptr(positions), ptr(sizes), i64(m), int(max_widen), ctypes.c_float(min_weight), ctypes.c_float(fill), ptr(out),
+        ptr(weight), ptr(widen))
+    return (out, weight, widen) if return_info else out
+
+
 def decode_mlp_at(code, shifts, w1, b1, w2, b2, w3, rows=None, voxel_sizes=None, gradient=False):
     """UNet5.decode(shifts, code[rows]) (net_definitions_torch.py:655-666) -> values [M,2]; with gradient=True
     (values, grad [M,3]) where grad is decode_with_gradient's d values[:,0] / d shift (:668-686, unscaled).

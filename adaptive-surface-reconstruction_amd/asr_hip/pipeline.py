@@ -85,6 +85,7 @@ class ImplicitPipeline:
             for d in range(t.ndim):
                 self._table[i].shape[d] = t.shape[d]
         self.sizes = None
+        self._bb = None
 
     def _params(self, bb_min, bb_max):
         p = ImplicitParams()
@@ -93,6 +94,7 @@ class ImplicitPipeline:
         for d in range(3):
             p.bb_min[d] = float(bb_min[d])
             p.bb_max[d] = float(bb_max[d])
+        self._bb = (tuple(p.bb_min), tuple(p.bb_max))  # the octree frame of this build / forward (transfer)
         p.scale_sdf = int(self.scale_sdf)
         p.precision = _lib.PRECISIONS[self.precision]
         return p
@@ -198,6 +200,29 @@ class ImplicitPipeline:
                       ptr(values), ptr(grad), ptr(rows))
         out = (values,) + ((grad,) if gradient else ()) + ((rows,) if return_rows else ())
         return out if len(out) > 1 else values
+
+    def transfer(self, points, radii, attributes, positions, **kw):
+        """Per-point attributes [N] or [N,C] of the cloud of the last forward carried onto positions [M,3], e.g. the
+        colours of a scan onto the mesh vertices (ops.point_attributes_at; keywords max_widen, min_weight, fill,
+        return_info go there).  `points` and `radii` are the ones given to forward (the radii before
+        point_radius_scale).  Every position is blended at the size of the grid-0 leaf that contains it -- the scale
+        at which the network looked at that place; positions outside the octree get `fill`.  Raises query's error
+        when there is no usable forward (none yet, a failed one, a build alone, a forward sharded over several ranks)."""
+        from . import ops
+        if not isinstance(positions, torch.Tensor):
+            positions = torch.from_numpy(np.ascontiguousarray(positions, dtype=np.float32))
+        positions = positions.to(self.device, torch.float32).contiguous()
+        if positions.ndim != 2 or positions.shape[1] != 3:
+            raise ValueError("positions must have shape [M,3]")
+        self._stream()
+        # the query's own test of the last forward (m = 0: nothing else happens)
+        self.ctx.call("asr_hip_implicit_query", ptr(positions), ctypes.c_int64(0), self._table, len(self._weights),
+                      ctypes.c_void_p(0), ctypes.c_void_p(0), ctypes.c_void_p(0))
+        frame = _lib.frame_init(*self._bb)
+        rows = ops.leaf_locate(frame, self.get("voxel_keys0"), positions).long()
+        sizes = torch.where(rows >= 0, self.get("voxel_sizes0")[rows.clamp(min=0)], torch.zeros((), device=self.device))
+        with torch.cuda.device(self.device):
+            return ops.point_attributes_at(frame, points, radii, attributes, positions, sizes, **kw)
 
     def get(self, name):
         """copy of one named array of the last forward (see include/asr_hip.h)"""

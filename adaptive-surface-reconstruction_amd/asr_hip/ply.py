@@ -8,9 +8,8 @@ _TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2
           "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def read_points(path):
-    """-> (points f32[N,3], normals f32[N,3], radii f32[N] or f32[0]).  ValueError if a required property is
-    missing (the reference returns empty arrays and then fails with "points is null!")."""
+def _read_vertex_table(path):
+    """-> ({property name: array [N]} of the vertex element, {property name: numpy type code})"""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError("%s: not a PLY file" % path)
@@ -60,9 +59,17 @@ def read_points(path):
                 dt = np.dtype([(n, order + t) for n, t in el["props"]])
                 rec = np.frombuffer(f.read(dt.itemsize * el["count"]), dtype=dt, count=el["count"])
                 data = {n: rec[n] for n in names}
+            types = dict(el["props"])
             break
     if data is None:
         raise ValueError("%s: no vertex element" % path)
+    return data, types
+
+
+def read_points(path):
+    """-> (points f32[N,3], normals f32[N,3], radii f32[N] or f32[0]).  ValueError if a required property is
+    missing (the reference returns empty arrays and then fails with "points is null!")."""
+    data, _ = _read_vertex_table(path)
     for req in ("x", "y", "z", "nx", "ny", "nz"):
         if req not in data:
             raise ValueError("%s: vertex property %s is missing (needed: x y z nx ny nz)" % (path, req))
@@ -76,52 +83,103 @@ def read_points(path):
     return points, normals, radii
 
 
-def write_points(path, points, normals, radii=None, binary=True):
-    """point cloud in the layout read_points takes (used by the tests and to export synthetic scans)"""
+def read_point_colors(path):
+    """-> uint8 [N,3], the vertex properties red green blue (or diffuse_red diffuse_green diffuse_blue) of a point
+    cloud, or None when the file has none.  Integer properties are taken as they are (clamped to 0..255), float
+    ones as 0..1 and scaled: round(clamp(c, 0, 1) * 255)."""
+    data, types = _read_vertex_table(path)
+    for names in (("red", "green", "blue"), ("diffuse_red", "diffuse_green", "diffuse_blue")):
+        if all(n in data for n in names):
+            cols = []
+            for n in names:
+                c = np.asarray(data[n], np.float64)
+                if types[n] in ("f4", "f8"):
+                    c = np.clip(c, 0.0, 1.0) * 255.0
+                cols.append(np.rint(np.clip(c, 0.0, 255.0)).astype(np.uint8))
+            return np.stack(cols, 1).reshape(-1, 3)
+    return None
+
+
+def _check_colors(colors, n, what):
+    c = np.asarray(colors)
+    if c.dtype != np.uint8 or c.ndim != 2 or c.shape != (n, 3):
+        raise ValueError("colors must be uint8 with one r g b row per %s" % what)
+    return c
+
+
+def _write_rows(f, fmt_binary, cols, colors):
+    """rows of float columns followed by three uchar colour columns (when given)"""
+    if colors is None:
+        if fmt_binary:
+            f.write(cols.astype("<f4").tobytes())
+        else:
+            np.savetxt(f, cols, fmt="%.9g")
+        return
+    if fmt_binary:
+        rec = np.empty(len(cols), dtype=[("f", "<f4", (cols.shape[1],)), ("c", "u1", (3,))])
+        rec["f"] = cols
+        rec["c"] = colors
+        f.write(rec.tobytes())
+    else:
+        np.savetxt(f, np.concatenate([cols.astype(np.float64), colors.astype(np.float64)], 1),
+                   fmt=["%.9g"] * cols.shape[1] + ["%d"] * 3)
+
+
+_COLOR_PROPS = "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+
+
+def write_points(path, points, normals, radii=None, binary=True, colors=None):
+    """point cloud in the layout read_points takes (used by the tests and to export synthetic scans); colors
+    uint8 [N,3] (optional) become the uchar properties red green blue, what read_point_colors reads"""
     points, normals = np.asarray(points, np.float32), np.asarray(normals, np.float32)
+    if colors is not None:
+        colors = _check_colors(colors, len(points), "point")
     cols = [points, normals] + ([np.asarray(radii, np.float32)[:, None]] if radii is not None and len(radii) else [])
     table = np.concatenate(cols, 1)
     props = ["x", "y", "z", "nx", "ny", "nz"] + (["radius"] if table.shape[1] == 7 else [])
     with open(path, "wb") as f:
         f.write(("ply\nformat %s 1.0\nelement vertex %d\n" % ("binary_little_endian" if binary else "ascii", len(table))).encode())
         f.write("".join("property float %s\n" % p for p in props).encode())
+        if colors is not None:
+            f.write(_COLOR_PROPS.encode())
         f.write(b"end_header\n")
-        if binary:
-            f.write(table.astype("<f4").tobytes())
-        else:
-            np.savetxt(f, table, fmt="%.9g")
+        _write_rows(f, binary, table, colors)
 
 
-def write_mesh(path, vertices, triangles, binary=True, normals=None):
+def write_mesh(path, vertices, triangles, binary=True, normals=None, colors=None):
     """triangle mesh: vertices f32[M,3], triangles i32[T,3] (the result dict of reconstruct_surface); normals
-    f32[M,3] (optional) become the vertex properties nx ny nz"""
+    f32[M,3] (optional) become the vertex properties nx ny nz, colors uint8 [M,3] (optional) the uchar properties
+    red green blue after them"""
     v = np.asarray(vertices, np.float32).reshape(-1, 3)
     t = np.asarray(triangles, np.int32).reshape(-1, 3)
     nprops = ""
+    if colors is not None:
+        colors = _check_colors(colors, len(v), "vertex")
     if normals is not None:
         nrm = np.asarray(normals, np.float32).reshape(-1, 3)
         if len(nrm) != len(v):
             raise ValueError("normals must have one row per vertex")
         v = np.concatenate([v, nrm], 1)
         nprops = "property float nx\nproperty float ny\nproperty float nz\n"
+    if colors is not None:
+        nprops += _COLOR_PROPS
     with open(path, "wb") as f:
         f.write(("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
                  "element face %d\nproperty list uchar int vertex_indices\nend_header\n"
                  % ("binary_little_endian" if binary else "ascii", len(v), nprops, len(t))).encode())
+        _write_rows(f, binary, v, colors)
         if binary:
-            f.write(v.astype("<f4").tobytes())
             rec = np.empty(len(t), dtype=[("n", "u1"), ("i", "<i4", 3)])
             rec["n"] = 3
             rec["i"] = t
             f.write(rec.tobytes())
         else:
-            np.savetxt(f, v, fmt="%.9g")
             np.savetxt(f, np.concatenate([np.full((len(t), 1), 3), t], 1), fmt="%d")
 
 
-def read_mesh(path, with_normals=False):
-    """inverse of write_mesh (tests): (vertices, triangles), or (vertices, triangles, normals or None) with
-    with_normals=True"""
+def read_mesh(path, with_normals=False, with_colors=False):
+    """inverse of write_mesh (tests): (vertices, triangles); with_normals=True adds the normals (or None),
+    with_colors=True then the uint8 [M,3] colours (or None)"""
     with open(path, "rb") as f:
         header = []
         while True:
@@ -131,15 +189,24 @@ def read_mesh(path, with_normals=False):
                 break
         nv = int([h for h in header if h.startswith("element vertex")][0].split()[2])
         nt = int([h for h in header if h.startswith("element face")][0].split()[2])
-        cols = 6 if "property float nx" in header else 3
+        fcols = 6 if "property float nx" in header else 3
+        has_colors = "property uchar red" in header
+        cols = fcols + (3 if has_colors else 0)
         if "format ascii 1.0" in header:
-            v = np.loadtxt(f, dtype=np.float32, max_rows=nv, ndmin=2).reshape(-1, cols)
+            v = np.loadtxt(f, dtype=np.float64, max_rows=nv, ndmin=2).reshape(-1, cols)
+            c = v[:, fcols:].astype(np.uint8)
+            v = v[:, :fcols].astype(np.float32)
             t = np.loadtxt(f, dtype=np.int32, max_rows=nt, ndmin=2).reshape(-1, 4)[:, 1:] if nt else np.zeros((0, 3), np.int32)
         else:
-            v = np.frombuffer(f.read(4 * cols * nv), "<f4").reshape(-1, cols)
+            dt = np.dtype([("f", "<f4", (fcols,))] + ([("c", "u1", (3,))] if has_colors else []))
+            rec = np.frombuffer(f.read(dt.itemsize * nv), dtype=dt)
+            v, c = rec["f"].reshape(-1, fcols), (rec["c"].reshape(-1, 3) if has_colors else None)
             rec = np.frombuffer(f.read(13 * nt), dtype=[("n", "u1"), ("i", "<i4", 3)])
             t = rec["i"].astype(np.int32)
     v = v.astype(np.float32)
+    out = (np.ascontiguousarray(v[:, :3]), t)
     if with_normals:
-        return np.ascontiguousarray(v[:, :3]), t, (np.ascontiguousarray(v[:, 3:]) if cols == 6 else None)
-    return np.ascontiguousarray(v[:, :3]), t
+        out += (np.ascontiguousarray(v[:, 3:]) if fcols == 6 else None,)
+    if with_colors:
+        out += (np.ascontiguousarray(c) if has_colors else None,)
+    return out

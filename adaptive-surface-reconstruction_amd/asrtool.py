@@ -3,6 +3,7 @@ reference (cpp/bin/main.cpp:114-177: `asrtool --in point_cloud.ply --out mesh.pl
 `--third-party-notices`) on top of adaptivesurfacereconstruction.reconstruct_surface.
 
     python adaptive-surface-reconstruction_amd/asrtool.py --in scan.ply --out mesh.ply [--weights model.pt] [--precision NAME]
+                                                          [--normals] [--colors]
 
 The reference bundles its network as <resource dir>/model.pt (cpp/lib/asr.cpp:138-139); here the weights come
 from --weights (a TorchScript archive with the same tensor names, a pickled state dict or an .npz) or from
@@ -21,6 +22,7 @@ Options:
     --weights FILE  Network weights (TorchScript model.pt, state dict .pt or .npz); default $ASR_RESOURCE_DIR
     --precision NAME  Arithmetic of the network's sparse convolutions: f32 (default), bf16x3_2acc, bf16x3, f16x2, f16
     --normals  Writes per-vertex normals (nx ny nz): the unit gradient of the network's field at each vertex
+    --colors  Carries the input's point colours (red green blue) onto the mesh vertices, blended at each vertex's own scale
     --version  Prints the version information
     --third-party-notices  Prints third-party software notices
 """
@@ -55,14 +57,24 @@ def main(argv=None):
     if precision not in _lib.PRECISIONS:
         sys.stderr.write("asrtool: unknown precision '%s' (one of %s)\n" % (precision, ", ".join(sorted(_lib.PRECISIONS))))
         return 1
-    import adaptivesurfacereconstruction as asr
     from asr_hip import ply
+    colors = None
+    if "--colors" in argv:  # before any GPU work: a cloud without colours is an error
+        colors = ply.read_point_colors(inp)
+        if colors is None:
+            sys.stderr.write("asrtool: --colors, but %s has no red/green/blue vertex properties\n" % inp)
+            return 1
+    import adaptivesurfacereconstruction as asr
     print("reading points")
     points, normals, radii = ply.read_points(inp)
     print("%d / %d" % (len(points), len(points)))
+    extra = {} if colors is None else {"point_attributes": colors.astype("float32")}
     result = asr.reconstruct_surface(points, normals, radii, weights=_option(argv, "--weights"), precision=precision,
-                                     vertex_normals="--normals" in argv)
-    ply.write_mesh(out, result["vertices"], result["triangles"], normals=result.get("vertex_normals"))
+                                     vertex_normals="--normals" in argv, **extra)
+    if colors is not None:
+        import numpy as np
+        colors = np.rint(np.clip(result["vertex_attributes"], 0, 255)).astype(np.uint8)
+    ply.write_mesh(out, result["vertices"], result["triangles"], normals=result.get("vertex_normals"), colors=colors)
     print("wrote %s: %d vertices, %d triangles" % (out, len(result["vertices"]), len(result["triangles"])))
     return 0
 

@@ -660,6 +660,23 @@ int asr_hip_leaf_locate(asr_hip_context* ctx, const asr_octree_frame* frame, con
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "leaf_locate: null argument");
     return asr_query_leaf_locate(ctx, frame, leaf_keys, num_leaves, positions, m, rows_out);
 }
+int asr_hip_point_attributes_at(asr_hip_context* ctx, const asr_octree_frame* frame, const float* points, const float* radii,
+                                int64_t n, const float* attributes, int c, const float* positions, const float* sizes,
+                                int64_t m, int max_widen, float min_weight, float fill, float* out, float* weight_out,
+                                int8_t* widen_out) {
+    CTX_GUARD(ctx);
+    if (n < 0 || m < 0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "point_attributes_at: negative size");
+    if (c < 1 || c > ASR_MAX_ATTRIBUTE_CHANNELS)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "point_attributes_at: %d attribute channels, supported are 1 to %d", c,
+                 ASR_MAX_ATTRIBUTE_CHANNELS);
+    if (max_widen < 0 || max_widen > 126) ASR_FAIL(ctx, ASR_HIP_EINVAL, "point_attributes_at: max_widen must be 0 to 126");
+    if (!(min_weight > 0.f)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "point_attributes_at: min_weight must be > 0");
+    if (!frame || (n > 0 && (!points || !radii || !attributes)) || (m > 0 && (!positions || !sizes || !out)))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "point_attributes_at: null argument");
+    ctx->scratch.reset();
+    return asr_geom_attributes_at(ctx, frame, points, radii, n, attributes, c, positions, sizes, m, max_widen, min_weight,
+                                  fill, out, weight_out, widen_out);
+}
 int asr_hip_decode_mlp_at(asr_hip_context* ctx, const float* code, int c, const int32_t* rows, const float* shifts,
                           int64_t m, const float* w1, const float* b1, int h1, const float* w2, const float* b2, int h2,
                           const float* w3, const float* sizes, float* values_out, float* grad_out) {

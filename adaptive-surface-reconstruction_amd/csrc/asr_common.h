@@ -477,6 +477,10 @@ int asr_geom_radius_fill(asr_hip_context* ctx, const float* pts, const float* ra
                          const float4** sorted_out = nullptr);
 int asr_geom_radius_neighbor_count(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts,
                                    const float* radii, i64 n, i64* counts_out);
+// attributes [n,c] blended at positions [m,3] with the aggregation's weight, widening per row (asr_hip_point_attributes_at)
+int asr_geom_attributes_at(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, const float* radii, i64 n,
+                           const float* attr, int c, const float* positions, const float* sizes, i64 m, int max_widen,
+                           float min_weight, float fill, float* out, float* weight_out, int8_t* widen_out);
 int asr_geom_knn(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, int k,
                  const float* radii_in, float radius_fraction, int outlier_threshold, float* radii_out,
                  uint8_t* inlier_out);

@@ -1157,6 +1157,150 @@ __global__ __launch_bounds__(256) void k_radius_query(asr_octree_frame f, const 
                                     s_pref[wave], s_beg[wave], s_keys[kw], s_pos[kw]);
 }
 
+// ------------------------------------------------------------------------------------------
+// Per-point attributes blended at arbitrary positions (asr_hip_point_attributes_at).  The search above with
+// nothing written per pair: one wave per query walks the 3^3 cells of radius_cells, every lane tests its candidates with the
+// search's predicate and keeps  sum w  and  sum w a[c]  in registers,
+//     w = (min(R, 2 r) / max(R, 2 r))^2 * clamp((1 - d / R^2)^3, 0, 1)       (k_radius_place's compat x k_agg_importance),
+// the wave adds the 64 partial sums with a fixed butterfly (same inputs, same bits) and, while the weight stays below
+// min_weight, goes on to R = 2 R, 4 R, ... itself -- a wave-uniform loop, no relaunch.  A long row is a longer loop.
+// sattr: the attributes in Morton order, CP (= C rounded up to 1, 2, 4, 8, 16) floats per point, so that the members of a
+// query -- neighbours in that order -- are read from adjacent, 4 CP byte aligned records.
+// ------------------------------------------------------------------------------------------
+template <int CP>
+__global__ void k_attr_permute(const float* attr, const int32_t* ids, i64 n, int c, float* sattr) {
+    const i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x;
+    if (i >= n * CP) return;
+    const i64 s = i / CP;
+    const int ch = (int)(i % CP);
+    sattr[i] = ch < c ? attr[(i64)ids[s] * c + ch] : 0.f;
+}
+// levels of the cell table: the finest any query starts on (k = 0) and the coarsest any can widen to (k = max_widen)
+__global__ __launch_bounds__(256) void k_attr_levels(asr_octree_frame f, const float* sizes, i64 m, float widen, int* cnt) {
+    __shared__ int s_lo[4], s_hi[4];
+    int lo = ASR_MAX_LEVEL, hi = 0;
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < m; i += (i64)gridDim.x * blockDim.x) {
+        const float s = sizes[i];
+        if (!(s > 0.f && s < INFINITY)) continue;  // such a row searches nothing
+        hi = max(hi, query_level(f, s));
+        lo = min(lo, query_level(f, s * widen));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = min(lo, __shfl_xor(lo, o, 64));
+        hi = max(hi, __shfl_xor(hi, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_lo[threadIdx.x >> 6] = lo;
+        s_hi[threadIdx.x >> 6] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicMin(&cnt[6], min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3])));
+        atomicMax(&cnt[7], max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3])));
+    }
+}
+template <int CP>
+__global__ __launch_bounds__(256) void k_attr_blend(asr_octree_frame f, const float4* __restrict__ sorted,
+                                                    const float* __restrict__ srad, const float* __restrict__ sattr,
+                                                    CellIndex ci, const float* __restrict__ positions,
+                                                    const float* __restrict__ sizes, i64 m, int c, int max_widen,
+                                                    float min_weight, float fill, float* __restrict__ out,
+                                                    float* __restrict__ weight_out, int8_t* __restrict__ widen_out) {
+    __shared__ int s_pref[4][28];
+    __shared__ int s_beg[4][27];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const i64 q = blockIdx.x * (i64)4 + wave;
+    if (q >= m) return;  // (no block-wide barrier below)
+    const float cx = positions[3 * q], cy = positions[3 * q + 1], cz = positions[3 * q + 2];
+    const float s = sizes[q];
+    int x21, y21, z21;
+    const bool ok = frame_coord21_checked(f, cx, cy, cz, x21, y21, z21) && s > 0.f && s < INFINITY;
+    float wsum = 0.f;
+    float acc[CP], lo[CP], hi[CP];  // sums, and the members' range per channel: the blend is clamped to it, so that rounding
+    int chosen = -1;                // never takes a convex combination out of its hull (a constant comes back exactly)
+    float r = s;
+    for (int k = 0; ok && k <= max_widen; ++k, r = r * 2.f) {
+        const float r2 = r * r;
+        const int total = radius_cells(f, ci, cx, cy, cz, r, lane, s_pref[wave], s_beg[wave]);
+        wsum = 0.f;
+#pragma unroll
+        for (int ch = 0; ch < CP; ++ch) {
+            acc[ch] = 0.f;
+            lo[ch] = INFINITY;
+            hi[ch] = -INFINITY;
+        }
+        for (int i0 = 0; i0 < total; i0 += 64) {
+            const int i = i0 + lane;
+            if (i >= total) continue;
+            int pos;
+            const float4 pt = radius_candidate<27>(sorted, s_pref[wave], s_beg[wave], i, &pos);
+            const float d = sqdist3(pt.x, pt.y, pt.z, cx, cy, cz);
+            if (!(d < r2)) continue;
+            const float bb = 2 * srad[pos];
+            const float ratio = fminf(r, bb) / fmaxf(r, bb);
+            const float t = 1.f - d / r2;
+            const float w = (ratio * ratio) * fminf(fmaxf(t * t * t, 0.f), 1.f);
+            if (!(w > 0.f)) continue;  // (a point on the rim)
+            wsum += w;
+            float av[CP];
+            if (CP >= 4) {
+#pragma unroll
+                for (int v = 0; v < CP / 4; ++v)
+                    reinterpret_cast<float4*>(av)[v] = reinterpret_cast<const float4*>(sattr + (size_t)pos * CP)[v];
+            } else {
+#pragma unroll
+                for (int ch = 0; ch < CP; ++ch) av[ch] = sattr[(size_t)pos * CP + ch];
+            }
+#pragma unroll
+            for (int ch = 0; ch < CP; ++ch) {
+                acc[ch] += w * av[ch];
+                lo[ch] = fminf(lo[ch], av[ch]);
+                hi[ch] = fmaxf(hi[ch], av[ch]);
+            }
+        }
+        // fixed-order butterfly: every lane ends with the same sums
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            wsum += __shfl_xor(wsum, o, 64);
+#pragma unroll
+            for (int ch = 0; ch < CP; ++ch) acc[ch] += __shfl_xor(acc[ch], o, 64);
+        }
+        __builtin_amdgcn_wave_barrier();  // the cell tables in LDS are rewritten for the next radius
+        if (wsum >= min_weight) {  // wave uniform
+            chosen = k;
+            break;
+        }
+    }
+    float mine = fill;
+    if (chosen >= 0) {
+        float mlo = 0.f, mhi = 0.f;
+#pragma unroll
+        for (int ch = 0; ch < CP; ++ch)
+            if (lane == ch) mine = acc[ch] / wsum;
+        // the range of this lane's channel over the wave (min and max are exact in any order)
+#pragma unroll
+        for (int ch = 0; ch < CP; ++ch) {
+            float l = lo[ch], h = hi[ch];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                l = fminf(l, __shfl_xor(l, o, 64));
+                h = fmaxf(h, __shfl_xor(h, o, 64));
+            }
+            if (lane == ch) {
+                mlo = l;
+                mhi = h;
+            }
+        }
+        mine = mine < mlo ? mlo : (mine > mhi ? mhi : mine);  // (a NaN stays a NaN)
+    }
+    if (lane < c) out[q * c + lane] = mine;
+    if (lane == 0) {
+        if (weight_out) weight_out[q] = chosen >= 0 ? wsum : 0.f;
+        if (widen_out) widen_out[q] = (int8_t)chosen;
+    }
+}
+
 // Cell ranges of the heavy rows, looked up ONCE per row (one wave each) and kept for the RADIUS_SPLIT x 4 waves of the
 // counting pass and of the filling pass, which used to repeat the 27 / 64 table look-ups each (2 x 2 x 10^8 probes at
 // 10 M points, three times the light rows' own)
@@ -3016,6 +3160,61 @@ int asr_geom_radius_neighbor_count(asr_hip_context* ctx, const asr_octree_frame*
                                       ctx->stream));
     ASR_TRY(read_flags(ctx, host));
     if (host[1]) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "cell table overflow");
+    return ASR_HIP_OK;
+}
+
+// asr_hip_point_attributes_at: the search's point index (Morton-ordered points and radii, cell table for the levels the
+// queries can reach), the attributes permuted into that order, then one fused search-and-blend launch.  Scratch: what the
+// index takes plus 4 CP n bytes; nothing per pair.  The index build reads its cell counts back (build_cell_table), as the
+// search's does; the blend itself is enqueued and not waited for.
+int asr_geom_attributes_at(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, const float* radii, i64 n,
+                           const float* attr, int c, const float* positions, const float* sizes, i64 m, int max_widen,
+                           float min_weight, float fill, float* out, float* weight_out, int8_t* widen_out) {
+    ASR_TRY(ensure_flags(ctx));
+    if (m <= 0) return ASR_HIP_OK;
+    if (n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "too many points for int32 indices");
+    int host[16];
+    ASR_TRY(fresh_flags(ctx));
+    const int init[2] = {ASR_MAX_LEVEL, 0};
+    ASR_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_flags + 6, init, 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    k_attr_levels<<<std::min<unsigned>(grid_for(m, BLK), 2048u), BLK, 0, ctx->stream>>>(*frame, sizes, m,
+                                                                                       std::ldexp(1.f, max_widen), ctx->d_flags);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(read_flags(ctx, host));
+    int lmin = host[6], lmax = host[7];
+    if (lmin > lmax) lmin = lmax = 0;  // no searchable row at all
+    const int cp = c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : c <= 8 ? 8 : 16;
+    RadiusState st;
+    st.cell_grow = rstate(ctx).cell_grow;
+    ArenaMark mark;
+    arena_mark(ctx->scratch, mark);
+    for (;;) {
+        ASR_TRY(build_point_index(ctx, frame, pts, n, lmin, lmax, st, nullptr, false, false, radii));
+        ASR_TRY(read_flags(ctx, host));
+        if (!host[1]) break;
+        if (st.cell_grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "radius search cell table overflow");
+        st.cell_grow += 2;  // lattice-like clouds crowd a few buckets (see TabProbe): a table four times the size
+        rstate(ctx).cell_grow = st.cell_grow;
+        arena_rewind(ctx->scratch, mark);
+    }
+    float* sattr = arena_alloc<float>(ctx->scratch, (size_t)(n + 1) * cp);
+    if (!sattr) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+#define ASR_ATTR_BLEND(CP_)                                                                                                  \
+    do {                                                                                                                     \
+        if (n > 0) k_attr_permute<CP_><<<grid_for(n * CP_, BLK), BLK, 0, ctx->stream>>>(attr, st.ids, n, c, sattr);         \
+        k_attr_blend<CP_><<<grid_for(m, 4), BLK, 0, ctx->stream>>>(*frame, st.sorted, st.srad, sattr, st.index(), positions, \
+                                                                   sizes, m, c, max_widen, min_weight, fill, out,            \
+                                                                   weight_out, widen_out);                                   \
+    } while (0)
+    switch (cp) {
+        case 1: ASR_ATTR_BLEND(1); break;
+        case 2: ASR_ATTR_BLEND(2); break;
+        case 4: ASR_ATTR_BLEND(4); break;
+        case 8: ASR_ATTR_BLEND(8); break;
+        default: ASR_ATTR_BLEND(16); break;
+    }
+#undef ASR_ATTR_BLEND
+    ASR_CHECK_LAUNCH(ctx);
     return ASR_HIP_OK;
 }
 

@@ -436,6 +436,28 @@ int asr_hip_decode_mlp_at(asr_hip_context* ctx, const float* code_dev, int c, co
                           const float* shifts_dev, int64_t m, const float* w1_dev, const float* b1_dev, int h1,
                           const float* w2_dev, const float* b2_dev, int h2, const float* w3_dev, const float* sizes_dev,
                           float* values_out_dev, float* grad_out_dev);
+/* ---- per-point attributes (colour, intensity, a label probability) blended at arbitrary positions ------------------ */
+/* For row j with position x and scale s = sizes[j], and k = 0, 1, ..., max_widen with R = s 2^k: the members are the points
+ * with d = ((dx*dx+dy*dy)+dz*dz) < R*R (the predicate of asr_hip_multi_radius_search), each with the weight
+ *     w = (min(R, 2 r)/max(R, 2 r))^2 * clamp((1 - d/R^2)^3, 0, 1)
+ * -- that search's scale compatibility for size R times the window of asr_hip_aggregation_importance on d/R^2 (radii_dev
+ * as given to the forward, before point_radius_scale).  With W_k = sum w, the row is sum(w a)/W_k of the first k whose
+ * W_k >= min_weight (> 0); weight_out[j] = that W_k, widen_out[j] = k.  Rows without such a k, non-finite positions,
+ * positions outside the frame's root cube and sizes that are not finite and > 0 get `fill`, weight 0 and widen -1.
+ * A convex combination of the members' attributes, clamped per channel to the range of the members with w > 0 (rounding
+ * never takes it out of their hull; a constant comes back exactly); non-finite attributes propagate.  The same inputs give
+ * the same bits.
+ * attributes_dev [n,c] with 1 <= c <= ASR_MAX_ATTRIBUTE_CHANNELS, out_dev [m,c]; weight_out_dev [m] and widen_out_dev [m]
+ * may be NULL; n = 0 and m = 0 are valid; max_widen 0..126.  For mesh vertices, sizes are the voxel sizes of the grid-0
+ * rows asr_hip_leaf_locate / asr_hip_implicit_query return.  One fused kernel on the context's stream, nothing sized by
+ * the number of pairs; scratch (context arena): the search's point index plus 4 c' n bytes (c' = c rounded up to a power
+ * of two).  The index build reads its per-level cell counts back, the blend itself is not waited for. */
+#define ASR_MAX_ATTRIBUTE_CHANNELS 16
+int asr_hip_point_attributes_at(asr_hip_context* ctx, const asr_octree_frame* frame, const float* points_dev,
+                                const float* radii_dev, int64_t n, const float* attributes_dev, int c,
+                                const float* positions_dev, const float* sizes_dev, int64_t m, int max_widen,
+                                float min_weight, float fill, float* out_dev, float* weight_out_dev,
+                                int8_t* widen_out_dev);
 /* (asr_hip_implicit_query, the whole-path query on the last forward, is declared after asr_hip_implicit_stage_ms) */
 
 /* ---- whole path: the section of asr::ReconstructSurface between the pre-filter and the
