@@ -296,3 +296,59 @@ class KDTree:
         cnt = _ops.radius_neighbor_count(self._frame, self._points,
                                          torch.from_numpy(radii).to(self._points.device))
         return [int(c) for c in cnt.cpu().tolist()]
+
+    def nearest(self, queries):
+        """Not in the reference's module.  For each query [M,3] the nearest point of the tree, exactly (brute-force
+        result in f32, ties to the smallest index; queries may lie anywhere, a non-finite one gets -1 and inf)
+        -> (index int32 [M], distance f32 [M])"""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != 3:
+            raise ValueError("queries must have shape [M,3]")
+        idx, sq = _ops.nearest_point(self._frame, self._points, torch.from_numpy(queries).to(self._points.device))
+        return idx.cpu().numpy(), np.sqrt(sq.cpu().numpy())
+
+
+def default_thresholds(reference_points):
+    """0.5 % and 1 % of the diagonal of the reference's bounding box: the F-score thresholds used when none are given"""
+    p = np.asarray(reference_points, np.float64).reshape(-1, 3)
+    diag = float(np.linalg.norm(p.max(0) - p.min(0)))
+    return (0.005 * diag, 0.01 * diag)
+
+
+def evaluate_mesh(vertices, triangles, reference_points=None, reference_normals=None, reference_mesh=None,
+                  num_samples=1_000_000, thresholds=None, seed=0):
+    """Not in the reference's module.  How far is the mesh from a reference surface: accuracy, completeness, Chamfer
+    (L1, L2), Hausdorff, precision / recall / F-score per threshold and -- when the reference has normals -- normal
+    consistency, between num_samples area-weighted samples of the mesh and either `reference_points` [N,3] (with
+    optional unit `reference_normals`) or num_samples samples of `reference_mesh` = (vertices, triangles).
+    Definitions: asr_hip.metrics.  thresholds None: 0.5 % and 1 % of the diagonal of the reference's bounding box
+    (its points, or the vertices of its mesh).  -> dict of Python floats (lists of floats per threshold)."""
+    from asr_hip import metrics as _metrics
+    vertices = _f32(vertices, "vertices", "[V,3]", 2, 3)
+    triangles = np.ascontiguousarray(triangles, dtype=np.int32)
+    if triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError("triangles must have shape [T,3]")
+    if (reference_points is None) == (reference_mesh is None):
+        raise ValueError("give exactly one of reference_points and reference_mesh")
+    dev = torch.device("cuda")
+    if reference_mesh is not None:
+        rv = _f32(reference_mesh[0], "reference_mesh vertices", "[V,3]", 2, 3)
+        rt = np.ascontiguousarray(reference_mesh[1], dtype=np.int32)
+        if rt.ndim != 2 or rt.shape[1] != 3:
+            raise ValueError("reference_mesh triangles must have shape [T,3]")
+        box, reference = rv, (torch.from_numpy(rv).to(dev), torch.from_numpy(rt).to(dev))
+    else:
+        rp = _f32(reference_points, "reference_points", "[N,3]", 2, 3)
+        rn = None
+        if reference_normals is not None:
+            rn = _f32(reference_normals, "reference_normals", "[N,3]", 2, 3)
+            if rn.shape != rp.shape:
+                raise ValueError("reference_normals must have shape [N,3]")
+            rn = torch.from_numpy(rn).to(dev)
+        box, reference = rp, (torch.from_numpy(rp).to(dev), rn)
+    if box.shape[0] == 0:
+        raise ValueError("the reference is empty")
+    if thresholds is None:
+        thresholds = default_thresholds(box)
+    return _metrics.mesh_metrics(torch.from_numpy(vertices).to(dev), torch.from_numpy(triangles).to(dev), reference,
+                                 int(num_samples), tuple(float(t) for t in thresholds), seed=int(seed))

@@ -636,6 +636,51 @@ def point_attributes_at(frame, points, radii, attributes, positions, sizes, max_
     return (out, weight, widen) if return_info else out
 
 
+def nearest_point(frame, points, queries):
+    """For each query [M,3] the nearest of `points` [N,3], another set (asr_hip_nearest_point): exactly the result of a
+    brute-force search with d2 = ((dx*dx + dy*dy) + dz*dz) in f32, ties to the smallest point index.  The frame only
+    defines the acceleration grid: queries may lie anywhere.  A non-finite query gets index -1 and distance +inf.
+    -> (index int32 [M], squared distance f32 [M])"""
+    points = _dev(points, torch.float32)
+    queries = _dev(queries, torch.float32)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError("points must have shape [N,3]")
+    if queries.ndim != 2 or queries.shape[1] != 3:
+        raise ValueError("queries must have shape [M,3]")
+    n, m = points.shape[0], queries.shape[0]
+    index = torch.empty(m, dtype=torch.int32, device=points.device)
+    sqdist = torch.empty(m, dtype=torch.float32, device=points.device)
+    context(_same_device(points, queries)).call("asr_hip_nearest_point", ctypes.byref(frame), ptr(points), i64(n),
+                                                ptr(queries), i64(m), ptr(index), ptr(sqdist))
+    return index, sqdist
+
+
+def mesh_sample(vertices, triangles, num_samples, seed=0, normals=False, return_triangle=False):
+    """num_samples points on the triangle mesh (vertices f32 [V,3], triangles int32 [T,3]), area weighted, stratified and
+    a pure function of the arguments (asr_hip_mesh_sample) -> points f32 [S,3]; normals=True adds the unit face normals
+    f32 [S,3] (corner order), return_triangle=True the triangle of each sample, int32 [S] (in that order)."""
+    vertices = _dev(vertices, torch.float32)
+    triangles = _dev(triangles, torch.int32)
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must have shape [V,3]")
+    if triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError("triangles must have shape [T,3]")
+    s = int(num_samples)
+    if s < 0:
+        raise ValueError("num_samples must be >= 0")
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must fit an unsigned 64-bit integer")
+    dev = _same_device(vertices, triangles)
+    points = torch.empty((s, 3), dtype=torch.float32, device=dev)
+    nrm = torch.empty((s, 3), dtype=torch.float32, device=dev) if normals else None
+    tri = torch.empty(s, dtype=torch.int32, device=dev) if return_triangle else None
+    context(dev).call("asr_hip_mesh_sample", ptr(vertices), i64(vertices.shape[0]), ptr(triangles),
+                      i64(triangles.shape[0]), i64(s), ctypes.c_uint64(seed), ptr(points), ptr(nrm), ptr(tri))
+    out = (points,) + ((nrm,) if normals else ()) + ((tri,) if return_triangle else ())
+    return out[0] if len(out) == 1 else out
+
+
 def decode_mlp_at(code, shifts, w1, b1, w2, b2, w3, rows=None, voxel_sizes=None, gradient=False):
     """UNet5.decode(shifts, code[rows]) (net_definitions_torch.py:655-666) -> values [M,2]; with gradient=True
     (values, grad [M,3]) where grad is decode_with_gradient's d values[:,0] / d shift (:668-686, unscaled).

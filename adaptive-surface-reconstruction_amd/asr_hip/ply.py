@@ -210,3 +210,31 @@ def read_mesh(path, with_normals=False, with_colors=False):
     if with_colors:
         out += (np.ascontiguousarray(c) if has_colors else None,)
     return out
+
+
+def read_surface(path):
+    """A surface to compare against (asrtool --compare): -> (vertices f32 [N,3], triangles i32 [T,3] or None, normals
+    f32 [N,3] or None).  A file with a non-empty face element is a triangle mesh in the layout write_mesh produces; one
+    without faces is a point cloud, whose nx ny nz are returned when present."""
+    faces = 0
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("%s: not a PLY file" % path)
+        for line in f:
+            tok = line.decode("ascii", "replace").split()
+            if tok[:2] == ["element", "face"]:
+                faces = int(tok[2])
+            if tok[:1] == ["end_header"]:
+                break
+    if faces > 0:
+        v, t, n = read_mesh(path, with_normals=True)
+        return v, t, n
+    data, _ = _read_vertex_table(path)
+    for req in ("x", "y", "z"):
+        if req not in data:
+            raise ValueError("%s: vertex property %s is missing" % (path, req))
+    points = np.stack([data["x"], data["y"], data["z"]], 1).astype(np.float32)
+    normals = None
+    if all(k in data for k in ("nx", "ny", "nz")):
+        normals = np.stack([data["nx"], data["ny"], data["nz"]], 1).astype(np.float32)
+    return points, None, normals

@@ -4,6 +4,7 @@ reference (cpp/bin/main.cpp:114-177: `asrtool --in point_cloud.ply --out mesh.pl
 
     python adaptive-surface-reconstruction_amd/asrtool.py --in scan.ply --out mesh.ply [--weights model.pt] [--precision NAME]
                                                           [--normals] [--colors]
+    python adaptive-surface-reconstruction_amd/asrtool.py --compare mesh.ply reference.ply [--samples N] [--thresholds a,b,...] [--seed S]
 
 The reference bundles its network as <resource dir>/model.pt (cpp/lib/asr.cpp:138-139); here the weights come
 from --weights (a TorchScript archive with the same tensor names, a pickled state dict or an .npz) or from
@@ -23,6 +24,12 @@ Options:
     --precision NAME  Arithmetic of the network's sparse convolutions: f32 (default), bf16x3_2acc, bf16x3, f16x2, f16
     --normals  Writes per-vertex normals (nx ny nz): the unit gradient of the network's field at each vertex
     --colors  Carries the input's point colours (red green blue) onto the mesh vertices, blended at each vertex's own scale
+    --compare MESH.ply REFERENCE.ply  Instead of reconstructing: prints one JSON line with the distance between the mesh
+              and the reference (accuracy, completeness, Chamfer, Hausdorff, precision / recall / F-score, normal consistency).
+              A REFERENCE with faces is a mesh; without faces it is a point cloud (nx ny nz are used if present)
+    --samples N  --compare: points sampled on each mesh (default 1000000)
+    --thresholds a,b,...  --compare: F-score distances (default: 0.5 % and 1 % of the reference's bounding-box diagonal)
+    --seed S  --compare: seed of the sampling (default 0)
     --version  Prints the version information
     --third-party-notices  Prints third-party software notices
 """
@@ -37,6 +44,45 @@ def _option(argv, name):
     return None
 
 
+def _compare(argv):
+    """--compare MESH.ply REFERENCE.ply: one JSON line, 0; a message on stderr and 1 when something is wrong"""
+    import json
+    i = argv.index("--compare")
+    paths = argv[i + 1:i + 3]
+    if len(paths) < 2 or any(p.startswith("--") for p in paths):
+        sys.stderr.write("asrtool: --compare needs two files: MESH.ply REFERENCE.ply\n")
+        return 1
+    for p in paths:
+        if not os.path.isfile(p):
+            sys.stderr.write("asrtool: --compare: no such file: %s\n" % p)
+            return 1
+    try:
+        samples = int(_option(argv, "--samples") or 1000000)
+        seed = int(_option(argv, "--seed") or 0)
+        thresholds = _option(argv, "--thresholds")
+        thresholds = None if thresholds is None else tuple(float(t) for t in thresholds.split(","))
+        if samples < 1 or seed < 0 or (thresholds is not None and not all(t > 0 for t in thresholds)):
+            raise ValueError("out of range")
+    except ValueError:
+        sys.stderr.write("asrtool: --compare: --samples and --seed take integers (N >= 1, S >= 0), --thresholds positive numbers a,b,...\n")
+        return 1
+    from asr_hip import ply
+    try:
+        v, t, _ = ply.read_surface(paths[0])
+        rv, rt, rn = ply.read_surface(paths[1])
+    except (ValueError, IndexError, OSError) as e:
+        sys.stderr.write("asrtool: --compare: %s\n" % e)
+        return 1
+    if t is None:
+        sys.stderr.write("asrtool: --compare: %s has no faces (the first file must be a mesh)\n" % paths[0])
+        return 1
+    import adaptivesurfacereconstruction as asr
+    ref = {"reference_mesh": (rv, rt)} if rt is not None else {"reference_points": rv, "reference_normals": rn}
+    result = asr.evaluate_mesh(v, t, num_samples=samples, thresholds=thresholds, seed=seed, **ref)
+    print(json.dumps(result))
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -48,6 +94,8 @@ def main(argv=None):
         import adaptivesurfacereconstruction as asr
         print(asr.get_third_party_notices())
         return 0
+    if "--compare" in argv:
+        return _compare(argv)
     inp, out = _option(argv, "--in"), _option(argv, "--out")
     if inp is None or out is None:
         sys.stdout.write(HELP)

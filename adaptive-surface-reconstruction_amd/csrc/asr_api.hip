@@ -686,6 +686,29 @@ int asr_hip_decode_mlp_at(asr_hip_context* ctx, const float* code, int c, const 
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "decode_mlp_at: null argument");
     return asr_query_decode_at(ctx, code, c, rows, shifts, m, w1, b1, h1, w2, b2, h2, w3, sizes, values_out, grad_out);
 }
+int asr_hip_nearest_point(asr_hip_context* ctx, const asr_octree_frame* frame, const float* points, int64_t n,
+                          const float* queries, int64_t m, int32_t* index_out, float* sqdist_out) {
+    CTX_GUARD(ctx);
+    if (n < 1 || n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "nearest_point: 1 <= n < 2^31 points are required");
+    if (m < 0 || m >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "nearest_point: 0 <= m < 2^31 queries are required");
+    if (!frame || !points || (m > 0 && !queries)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "nearest_point: null argument");
+    ctx->scratch.reset();
+    return asr_geom_nearest(ctx, frame, points, n, queries, m, index_out, sqdist_out);
+}
+int asr_hip_mesh_sample(asr_hip_context* ctx, const float* vertices, int64_t num_vertices, const int32_t* triangles,
+                        int64_t num_triangles, int64_t num_samples, uint64_t seed, float* points_out, float* normals_out,
+                        int32_t* triangle_out) {
+    CTX_GUARD(ctx);
+    if (num_vertices < 0 || num_triangles < 0 || num_samples < 0)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_sample: negative size");
+    if (num_vertices >= (i64(1) << 31) || num_triangles >= (i64(1) << 31) / 3)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_sample: mesh does not fit 32-bit indices");
+    if ((num_triangles > 0 && (!triangles || (num_vertices > 0 && !vertices))) || (num_samples > 0 && !points_out))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_sample: null argument");
+    ctx->scratch.reset();
+    return asr_mesh_sample(ctx, vertices, num_vertices, triangles, num_triangles, num_samples, seed, points_out,
+                           normals_out, triangle_out);
+}
 
 }  // extern "C"
 

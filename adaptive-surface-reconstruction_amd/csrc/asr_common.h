@@ -484,6 +484,9 @@ int asr_geom_attributes_at(asr_hip_context* ctx, const asr_octree_frame* frame, 
 int asr_geom_knn(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, int k,
                  const float* radii_in, float radius_fraction, int outlier_threshold, float* radii_out,
                  uint8_t* inlier_out);
+// nearest point of each query among pts (exact, ties to the smallest index); either output may be null
+int asr_geom_nearest(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, const float* queries,
+                     i64 m, int32_t* index_out, float* sqdist_out);
 int asr_geom_dual_count(asr_hip_context* ctx, const u64* nodes, i64 num_nodes, const u64* leaves, i64 num_leaves,
                         i64* num_cells);
 int asr_geom_dual_fill(asr_hip_context* ctx, i64* out);
@@ -499,6 +502,9 @@ int asr_mesh_contour_fill(asr_hip_context* ctx, float* vertices, int32_t* triang
 int asr_mesh_components_count(asr_hip_context* ctx, const float* vertices, i64 nv, const int32_t* triangles,
                               i64 nt, i64 keep_n, i64 min_size, i64* nv_out, i64* nt_out);
 int asr_mesh_components_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out);
+// stratified area-weighted samples of a triangle mesh (asr_hip_mesh_sample); normals / tri may be null
+int asr_mesh_sample(asr_hip_context* ctx, const float* vertices, i64 nv, const int32_t* triangles, i64 nt, i64 num_samples,
+                    u64 seed, float* points, float* normals, int32_t* tri);
 void asr_mesh_release(asr_hip_context* ctx);
 
 int asr_conv_agg_importance(asr_hip_context* ctx, const float* compat, const float* dist, i64 n,

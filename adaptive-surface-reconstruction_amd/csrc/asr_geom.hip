@@ -1860,6 +1860,141 @@ __global__ __launch_bounds__(256) void k_knn_cells(asr_octree_frame f, const flo
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Nearest point of ANOTHER set (asr_hip_nearest_point): one wave per query, queries taken in Morton order so that
+// neighbouring waves probe the same cells.  Level by level, finest first, like k_knn: lanes 0..26 look up the 3^3 block
+// around the query's cell, the wave walks the block's points 64 at a time and keeps the smallest (squared distance
+// bits, point index) key -- ties go to the smallest index.
+// A query need not lie in the centre cell of its block (one outside the root cube was clamped into a boundary cell), so
+// k_knn's "d <= (cell size)^2" does not apply.  What holds for every query: a point that is NOT in the block lies beyond
+// one of the block's six faces, so it is at least as far away as that face.  The result of a level is exact when it is
+// closer than the nearest face; faces on the root cube's boundary do not count (points beyond them were clamped into
+// the boundary cells, which the block holds).  Level 0 is the whole cloud.
+// Rounding: a point is binned by floor(fl(p * inv)) and the face position is computed as fl(fl(c) * voxel_size), where
+// inv * voxel_size = 1 +- 2^-23.  A point beyond the face at integer coordinate c has p < F + |F| 2^-23 with F = c / inv,
+// the computed face f is within |F| 2^-22 of F, and sqdist3 loses at most 2^-22 relative: the gap q - f is shrunk to
+// (q - f)(1 - 2^-20) - |f| 2^-20, which covers all of it several times over.
+// ------------------------------------------------------------------------------------------
+// floor(t) + off clamped into [0, 2^21): k_point_codes' cell for points of the cube, the nearest boundary cell outside
+__device__ inline int clamped_cell21(float t, int off) {
+    const float ft = fminf(fmaxf(floorf(t), -4.0e9f), 4.0e9f);
+    const i64 c = (i64)ft + off, lim = (1 << ASR_MAX_LEVEL) - 1;
+    return (int)(c < 0 ? 0 : c > lim ? lim : c);
+}
+__device__ inline bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+__global__ void k_query_codes(asr_octree_frame f, const float* q, i64 m, u64* codes, int32_t* ids) {
+    const i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const float qx = q[3 * i], qy = q[3 * i + 1], qz = q[3 * i + 2];
+    const float inv = f.inv_voxel_size[ASR_MAX_LEVEL];
+    u64 code = (u64(1) << 63) - 1;  // non-finite rows last
+    if (finite3(qx, qy, qz))
+        code = asr_morton3d((u64)clamped_cell21(qx * inv, f.offset[0]), (u64)clamped_cell21(qy * inv, f.offset[1]),
+                            (u64)clamped_cell21(qz * inv, f.offset[2]));
+    codes[i] = code;
+    ids[i] = (int32_t)i;
+}
+// distance from q to the nearer of the block's two faces on one axis, shrunk by the rounding margin; +inf for a face
+// on the root cube's boundary, negative when q lies outside the block.  c = centre cell of the block on `lev`.
+__device__ inline float nearest_face_gap(const asr_octree_frame& f, float q, int c, int lev, int off) {
+    const int s = ASR_MAX_LEVEL - lev;
+    const float vs = f.voxel_size[ASR_MAX_LEVEL];
+    const float keep = 0.99999904632568359375f, slack = 9.5367431640625e-7f;  // 1 - 2^-20, 2^-20
+    float g = __uint_as_float(0x7f800000u);
+    if (c - 1 > 0) {
+        const float face = (float)(((i64)(c - 1) << s) - off) * vs;
+        g = fminf(g, (q - face) * keep - fabsf(face) * slack);
+    }
+    if (c + 2 < (1 << lev)) {
+        const float face = (float)(((i64)(c + 2) << s) - off) * vs;
+        g = fminf(g, (face - q) * keep - fabsf(face) * slack);
+    }
+    return g;
+}
+__global__ __launch_bounds__(256) void k_nearest(asr_octree_frame f, const float4* __restrict__ sorted, CellIndex ci,
+                                                 int lfine, int ldeep, const float* __restrict__ queries,
+                                                 const int32_t* __restrict__ order, i64 m, int32_t* index_out,
+                                                 float* sqdist_out) {
+    __shared__ int s_pref[4][28];
+    __shared__ int s_beg[4][28];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const i64 w = blockIdx.x * (i64)4 + wave;
+    if (w >= m) return;
+    const i64 j = order[w];
+    const float qx = queries[3 * j], qy = queries[3 * j + 1], qz = queries[3 * j + 2];
+    if (!finite3(qx, qy, qz)) {
+        if (lane == 0) {
+            if (index_out) index_out[j] = -1;
+            if (sqdist_out) sqdist_out[j] = __uint_as_float(0x7f800000u);
+        }
+        return;
+    }
+    const float inv = f.inv_voxel_size[ASR_MAX_LEVEL];
+    const int cx = clamped_cell21(qx * inv, f.offset[0]), cy = clamped_cell21(qy * inv, f.offset[1]),
+              cz = clamped_cell21(qz * inv, f.offset[2]);
+    // start level: as in k_knn, a query whose finest-level cell is crowded starts on the level at which its cell holds
+    // at most KNN_CROWD points (the codes are sorted down to ldeep)
+    int lev0 = lfine;
+    if (ldeep > lfine) {
+        const u64 code = asr_morton3d((u64)cx, (u64)cy, (u64)cz);
+        int b0, pop;
+        cell_range(ci, code >> (3 * (ASR_MAX_LEVEL - lfine)), lfine, b0, pop);
+        while (pop > KNN_CROWD && lev0 < ldeep) {
+            ++lev0;
+            cell_range(ci, code >> (3 * (ASR_MAX_LEVEL - lev0)), lev0, b0, pop);
+        }
+    }
+    u64 best = ~u64(0);  // (squared distance bits << 32) | original point index
+    for (int lev = lev0; lev >= 0; --lev) {
+        const int s = ASR_MAX_LEVEL - lev, lim = (1 << lev) - 1;
+        const int x = cx >> s, y = cy >> s, z = cz >> s;
+        int b = 0, cnt = 0;
+        if (lane < 27) {
+            const int xx = x + lane % 3 - 1, yy = y + (lane / 3) % 3 - 1, zz = z + lane / 9 - 1;
+            if (xx >= 0 && yy >= 0 && zz >= 0 && xx <= lim && yy <= lim && zz <= lim)
+                cell_range(ci, asr_morton3d((u64)xx, (u64)yy, (u64)zz), lev, b, cnt);
+        }
+        int pre = cnt;
+#pragma unroll
+        for (int o = 1; o < 32; o <<= 1) {
+            const int up = __shfl_up(pre, o, 64);
+            if (lane >= o) pre += up;
+        }
+        const int total = __shfl(pre, 26, 64);
+        if (total == 0) continue;  // (level 0 holds all n >= 1 points)
+        __builtin_amdgcn_wave_barrier();
+        if (lane < 27) {
+            s_pref[wave][lane + 1] = pre;
+            s_beg[wave][lane] = b;
+        }
+        if (lane == 0) s_pref[wave][0] = 0;
+        __builtin_amdgcn_wave_barrier();
+        for (int i0 = 0; i0 < total; i0 += 64) {
+            const int i = i0 + lane;
+            if (i < total) {
+                const float4 pt = radius_candidate(sorted, s_pref[wave], s_beg[wave], i);
+                const u64 key = ((u64)__float_as_uint(sqdist3(pt.x, pt.y, pt.z, qx, qy, qz)) << 32) |
+                                (u64)(u32)__float_as_int(pt.w);
+                best = key < best ? key : best;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const u32 hi = __shfl_xor((u32)(best >> 32), o, 64), lo = __shfl_xor((u32)best, o, 64);
+            const u64 other = ((u64)hi << 32) | lo;
+            best = other < best ? other : best;
+        }
+        if (lev == 0) break;
+        const float g = fminf(fminf(nearest_face_gap(f, qx, x, lev, f.offset[0]), nearest_face_gap(f, qy, y, lev, f.offset[1])),
+                              nearest_face_gap(f, qz, z, lev, f.offset[2]));
+        if (g > 0.f && __uint_as_float((u32)(best >> 32)) < g * g) break;
+    }
+    if (lane == 0) {
+        if (index_out) index_out[j] = (int32_t)(u32)best;
+        if (sqdist_out) sqdist_out[j] = __uint_as_float((u32)(best >> 32));
+    }
+}
+
 // rows are sorted by a segmented radix sort on (distance bits, index) keys; unpack + compat
 // ------------------------------------------------------------------------------------------
 // a11: CSR inversion
@@ -3299,6 +3434,55 @@ int asr_geom_knn(asr_hip_context* ctx, const asr_octree_frame* frame, const floa
     }
     ASR_TRY(read_flags(ctx, host));
     if (host[1]) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "cell table overflow");
+    return ASR_HIP_OK;
+}
+
+// asr_hip_nearest_point: the kNN search's point index (levels 0..lfine hashed, crowded clouds sorted eight levels
+// deeper), the queries' Morton order, one k_nearest launch.  Host round trips: the cell counts of the index build, the
+// largest cell population; the search itself is enqueued and not waited for.
+int asr_geom_nearest(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, const float* queries,
+                     i64 m, int32_t* index_out, float* sqdist_out) {
+    ASR_TRY(ensure_flags(ctx));
+    if (m <= 0 || (!index_out && !sqdist_out)) return ASR_HIP_OK;
+    int lfine = 1;
+    while (lfine < ASR_MAX_LEVEL - 1 && (i64(1) << (3 * lfine)) < n) ++lfine;
+    RadiusState st;
+    st.cell_grow = rstate(ctx).cell_grow;
+    int host[16];
+    ArenaMark mark;
+    arena_mark(ctx->scratch, mark);
+    for (;;) {
+        ASR_TRY(build_point_index(ctx, frame, pts, n, 0, lfine, st));
+        ASR_TRY(read_flags(ctx, host));
+        if (!host[1]) break;
+        if (st.cell_grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "nearest point: cell table overflow");
+        st.cell_grow += 2;  // lattice-like clouds crowd a few buckets (see TabProbe): a table four times the size
+        rstate(ctx).cell_grow = st.cell_grow;
+        arena_rewind(ctx->scratch, mark);
+    }
+    st.lhash = lfine;
+    int ldeep = lfine;
+    ASR_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags + 14, 0, sizeof(int), ctx->stream));
+    k_max_cell_pop<<<grid_for((i64)st.tab.mask + 1, BLK), BLK, 0, ctx->stream>>>(st.tab, st.start, st.end, lfine,
+                                                                               ctx->d_flags + 14);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(read_flags(ctx, host));
+    if (host[14] > KNN_CROWD && ctx->opt.knn_deep) {
+        ldeep = std::min<int>(ASR_MAX_LEVEL, lfine + 8);
+        ASR_TRY(deepen_point_index(ctx, pts, st, ldeep));
+    }
+    u64* qcodes_u = arena_alloc<u64>(ctx->scratch, m);
+    u64* qcodes = arena_alloc<u64>(ctx->scratch, m);
+    int32_t* qids_u = arena_alloc<int32_t>(ctx->scratch, m);
+    int32_t* qids = arena_alloc<int32_t>(ctx->scratch, m);
+    if (!qcodes_u || !qcodes || !qids_u || !qids) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    k_query_codes<<<grid_for(m, BLK), BLK, 0, ctx->stream>>>(*frame, queries, m, qcodes_u, qids_u);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY((sort_pairs<u64, int32_t>(ctx, ctx->scratch, qcodes_u, qcodes, qids_u, qids, m, 63,
+                                      3 * (ASR_MAX_LEVEL - lfine))));
+    k_nearest<<<grid_for(m, 4), BLK, 0, ctx->stream>>>(*frame, st.sorted, st.index(), lfine, ldeep, queries, qids, m,
+                                                       index_out, sqdist_out);
+    ASR_CHECK_LAUNCH(ctx);
     return ASR_HIP_OK;
 }
 

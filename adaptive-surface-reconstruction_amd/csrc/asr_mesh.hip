@@ -7,6 +7,7 @@
 // is a data-parallel map + exclusive scan that lands each item at the index the serial loop gives.
 // Compiled with -ffp-contract=off: the crossing points are double sums that must round like the
 // reference's.
+#include <cmath>
 #include <cstring>
 #include <algorithm>
 
@@ -428,6 +429,76 @@ __global__ void k_compact_triangles(const int32_t* in, i64 nt, const i64* voff, 
     for (int q = 0; q < 3; ++q) out[o * 3 + q] = (int32_t)voff[in[f * 3 + q]];
 }
 
+// ------------------------------------------------------------------------------------------
+// asr_hip_mesh_sample: stratified, area-weighted points on a triangle mesh.
+// Areas are f64 from the f32 corners, P = their inclusive prefix sums (fixed summation order), A = P[last].  Sample s owns
+// the stratum [s, s + 1) A / S of the parameter line: u = (s + r0) A / S, its triangle is the first t with P[t] > u -- a
+// zero-area triangle has P[t] == P[t - 1] and is never that one.  Inside the triangle b1 = sqrt(r1) (1 - r2),
+// b2 = sqrt(r1) r2 (uniform: the sqrt undoes the linear density of the distance to corner 0) and, in f32 without
+// contraction, p = v0 + b1 (v1 - v0) + b2 (v2 - v0): a coordinate all three corners share comes out exactly.
+// r0, r1, r2 are functions of (seed, s, stream) alone -- no state, no dependence on the launch:
+//   h = fmix64(fmix64(seed + 0x9E3779B97F4A7C15 (stream + 1)) ^ (s * 0xBF58476D1CE4E5B9)),  fmix64 = murmur3's finaliser
+//   r0 = (h >> 11) 2^-53 (f64, stream 0);  r1, r2 = (h >> 40) 2^-24 (f32, streams 1 and 2)
+// One thread per sample; the binary search reads log2(T) prefix sums, the top levels of which stay in L2.
+// ------------------------------------------------------------------------------------------
+__device__ inline u64 sample_hash(u64 seed, u64 s, u64 stream) {
+    return asr_hash64(asr_hash64(seed + 0x9E3779B97F4A7C15ull * (stream + 1)) ^ (s * 0xBF58476D1CE4E5B9ull));
+}
+__global__ void k_tri_areas(const float* vtx, i64 nv, const int32_t* tri, i64 nt, double* area, int* flags) {
+    const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nt) return;
+    const int a = tri[t * 3], b = tri[t * 3 + 1], c = tri[t * 3 + 2];
+    if (a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv) {
+        atomicOr(&flags[4], 1);
+        area[t] = 0.0;
+        return;
+    }
+    const double ax = vtx[3 * (i64)a], ay = vtx[3 * (i64)a + 1], az = vtx[3 * (i64)a + 2];
+    const double ux = vtx[3 * (i64)b] - ax, uy = vtx[3 * (i64)b + 1] - ay, uz = vtx[3 * (i64)b + 2] - az;
+    const double wx = vtx[3 * (i64)c] - ax, wy = vtx[3 * (i64)c + 1] - ay, wz = vtx[3 * (i64)c + 2] - az;
+    const double nx = uy * wz - uz * wy, ny = uz * wx - ux * wz, nz = ux * wy - uy * wx;
+    const double ar = 0.5 * sqrt(nx * nx + ny * ny + nz * nz);
+    area[t] = ar > 0.0 ? ar : 0.0;  // NaN corners: no area (an infinite one makes the total infinite: refused)
+}
+__global__ void k_mesh_sample(const float* __restrict__ vtx, const int32_t* __restrict__ tri, i64 nt,
+                              const double* __restrict__ prefix, i64 num_samples, u64 seed, float* points,
+                              float* normals, int32_t* tri_out) {
+    const i64 s = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= num_samples) return;
+    const double total = prefix[nt - 1];
+    const double r0 = (double)(sample_hash(seed, (u64)s, 0) >> 11) * 0x1p-53;
+    const float r1 = (float)(sample_hash(seed, (u64)s, 1) >> 40) * 0x1p-24f;
+    const float r2 = (float)(sample_hash(seed, (u64)s, 2) >> 40) * 0x1p-24f;
+    double u = ((double)s + r0) * total / (double)num_samples;
+    if (!(u < total)) u = total * (1.0 - 0x1p-52);  // rounding at the top end: the last triangle with an area
+    i64 lo = 0, hi = nt - 1;  // first t with prefix[t] > u (prefix[nt - 1] = total > u)
+    while (lo < hi) {
+        const i64 mid = (lo + hi) >> 1;
+        if (prefix[mid] > u)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    const i64 a = tri[lo * 3], b = tri[lo * 3 + 1], c = tri[lo * 3 + 2];
+    const float ax = vtx[3 * a], ay = vtx[3 * a + 1], az = vtx[3 * a + 2];
+    const float ux = vtx[3 * b] - ax, uy = vtx[3 * b + 1] - ay, uz = vtx[3 * b + 2] - az;
+    const float wx = vtx[3 * c] - ax, wy = vtx[3 * c + 1] - ay, wz = vtx[3 * c + 2] - az;
+    const float sr = sqrtf(r1);
+    const float b1 = sr * (1.f - r2), b2 = sr * r2;
+    points[3 * s] = ax + b1 * ux + b2 * wx;
+    points[3 * s + 1] = ay + b1 * uy + b2 * wy;
+    points[3 * s + 2] = az + b1 * uz + b2 * wz;
+    if (tri_out) tri_out[s] = (int32_t)lo;
+    if (normals) {
+        const double nx = (double)uy * wz - (double)uz * wy, ny = (double)uz * wx - (double)ux * wz,
+                     nz = (double)ux * wy - (double)uy * wx;
+        const double inv = 1.0 / sqrt(nx * nx + ny * ny + nz * nz);  // > 0: the triangle has an area
+        normals[3 * s] = (float)(nx * inv);
+        normals[3 * s + 1] = (float)(ny * inv);
+        normals[3 * s + 2] = (float)(nz * inv);
+    }
+}
+
 MeshState& mstate(asr_hip_context* ctx) {
     if (!ctx->mesh_state) ctx->mesh_state = new MeshState();
     return *(MeshState*)ctx->mesh_state;
@@ -632,5 +703,34 @@ int asr_mesh_components_fill(asr_hip_context* ctx, float* vertices_out, int32_t*
         ASR_CHECK_LAUNCH(ctx);
     }
     ASR_HIP_CHECK(ctx, hipStreamSynchronize(s));
+    return ASR_HIP_OK;
+}
+
+int asr_mesh_sample(asr_hip_context* ctx, const float* vertices, i64 nv, const int32_t* triangles, i64 nt, i64 num_samples,
+                    u64 seed, float* points, float* normals, int32_t* tri) {
+    ASR_TRY(ensure_flags(ctx));
+    hipStream_t s = ctx->stream;
+    double total = 0.0;
+    double* prefix = nullptr;
+    if (nt > 0) {  // the corner indices are checked whether or not samples are wanted
+        ASR_TRY(fresh_flags(ctx));
+        MESH_ALLOC(area, double, nt);
+        prefix = arena_alloc<double>(ctx->scratch, (size_t)nt);
+        if (!prefix) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+        k_tri_areas<<<grid_for(nt, BLK), BLK, 0, s>>>(vertices, nv, triangles, nt, area, ctx->d_flags);
+        ASR_CHECK_LAUNCH(ctx);
+        ASR_TRY(scan_f64_inclusive(ctx, ctx->scratch, area, prefix, nt));
+        ASR_HIP_CHECK(ctx, hipMemcpyAsync(&total, prefix + (nt - 1), sizeof(double), hipMemcpyDeviceToHost, s));
+        int host[16];
+        ASR_TRY(read_flags(ctx, host));
+        if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_sample: triangle index out of range");
+    }
+    if (num_samples == 0) return ASR_HIP_OK;
+    if (nt <= 0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_sample: no triangles to sample");
+    if (!(total > 0.0) || !std::isfinite(total))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_sample: the mesh's area is %g", total);
+    k_mesh_sample<<<grid_for(num_samples, BLK), BLK, 0, s>>>(vertices, triangles, nt, prefix, num_samples, seed, points,
+                                                              normals, tri);
+    ASR_CHECK_LAUNCH(ctx);
     return ASR_HIP_OK;
 }

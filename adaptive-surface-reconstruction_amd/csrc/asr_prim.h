@@ -79,6 +79,18 @@ static inline int scan_counts(asr_hip_context* ctx, Arena& arena, const i64* in,
                                                rocprim::plus<i64>(), ctx->stream));
     return ASR_HIP_OK;
 }
+// out[i] = in[0] + ... + in[i] in f64, summed in a fixed order (no look-back race): the same bits on every run
+static inline int scan_f64_inclusive(asr_hip_context* ctx, Arena& arena, const double* in, double* out, i64 n) {
+    if (n <= 0) return ASR_HIP_OK;
+    size_t tb = 0;
+    ASR_HIP_CHECK(ctx, rocprim::deterministic_inclusive_scan(nullptr, tb, in, out, (size_t)n, rocprim::plus<double>(),
+                                                             ctx->stream));
+    void* tmp = arena.alloc(tb ? tb : 256);
+    if (!tmp) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    ASR_HIP_CHECK(ctx, rocprim::deterministic_inclusive_scan(tmp, tb, in, out, (size_t)n, rocprim::plus<double>(),
+                                                             ctx->stream));
+    return ASR_HIP_OK;
+}
 static inline int read_i64(asr_hip_context* ctx, const i64* dev, i64* host) {
     ASR_HIP_CHECK(ctx, hipMemcpyAsync(host, dev, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
     ASR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));

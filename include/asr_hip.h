@@ -458,6 +458,29 @@ int asr_hip_point_attributes_at(asr_hip_context* ctx, const asr_octree_frame* fr
                                 const float* positions_dev, const float* sizes_dev, int64_t m, int max_widen,
                                 float min_weight, float fill, float* out_dev, float* weight_out_dev,
                                 int8_t* widen_out_dev);
+/* ---- comparing two surfaces: nearest point of another set, points sampled on a mesh (not in the reference) --------- */
+/* index_out[j] = the i that minimises d2(i, j), sqdist_out[j] = that minimum, with
+ *     d2(i, j) = ((px-qx)^2 + (py-qy)^2) + (pz-qz)^2 in f32 (the predicate arithmetic of asr_hip_multi_radius_search).
+ * Exact: the result of a brute-force search over all n points with that formula; ties go to the smallest point index.
+ * 1 <= n < 2^31 and 0 <= m < 2^31, else ASR_HIP_EINVAL; either output pointer may be NULL.  The frame only defines the
+ * acceleration grid (as for asr_hip_knn_radius): queries may lie anywhere, outside the frame too, and still get the
+ * exact answer (more slowly, the further from the points they are).  A query with a non-finite coordinate gets index -1
+ * and distance +inf; non-finite POINTS are ASR_HIP_EINVAL.  Plain stores, no float atomics: the same inputs give the
+ * same bits.  The index build reads its cell counts back; the search itself is not waited for. */
+int asr_hip_nearest_point(asr_hip_context* ctx, const asr_octree_frame* frame, const float* points_dev, int64_t n,
+                          const float* queries_dev, int64_t m, int32_t* index_out_dev, float* sqdist_out_dev);
+/* num_samples points on a triangle mesh, area weighted, stratified and deterministic.  Triangle areas are f64 from the f32
+ * corners, P their prefix sums, A the total.  Sample s takes u = (s + r0) A / S, the first triangle t with P[t] > u
+ * (triangles without area are never chosen), the barycentric coordinates b1 = sqrt(r1) (1 - r2), b2 = sqrt(r1) r2 and the
+ * point v0 + b1 (v1 - v0) + b2 (v2 - v0) in f32 without contraction (a triangle in a coordinate plane yields points
+ * exactly in that plane).  r0, r1, r2 in [0, 1) are a counter-based hash of (seed, s, stream): no state,
+ * the same bits for the same arguments.  normals_out_dev [S,3] (may be NULL): the unit normal of the sample's triangle,
+ * (v1 - v0) x (v2 - v0) normalised; triangle_out_dev [S] (may be NULL): its index.
+ * ASR_HIP_EINVAL: a corner index outside [0, num_vertices); num_samples > 0 with no triangles or with A == 0 (or not
+ * finite).  num_samples == 0 is valid.  Reads the total area back before the sampling kernel is enqueued. */
+int asr_hip_mesh_sample(asr_hip_context* ctx, const float* vertices_dev, int64_t num_vertices,
+                        const int32_t* triangles_dev, int64_t num_triangles, int64_t num_samples, uint64_t seed,
+                        float* points_out_dev, float* normals_out_dev, int32_t* triangle_out_dev);
 /* (asr_hip_implicit_query, the whole-path query on the last forward, is declared after asr_hip_implicit_stage_ms) */
 
 /* ---- whole path: the section of asr::ReconstructSurface between the pre-filter and the
