@@ -66,7 +66,9 @@ def test_aggregation_importance_and_continuous_conv(geo, gpu):
 
 
 def test_continuous_conv_ragged_and_long_rows(gpu):
-    """rows of 0 .. 6000 neighbours: rows above 1024 pairs take the 16-wave path"""
+    """rows of 0 .. 6000 neighbours: rows above 256 pairs (CCONV_HEAVY) take the 16-wave long-row kernels, which cut a
+    row into segments of 4096 pairs (CCH_SEG): 6000 is two segments.  The values next to these constants are in
+    tests/test_gpu_cconv.py."""
     from asr_hip import ops
     rng = np.random.default_rng(3)
     n, cin, cout = 8000, 4, 32
