@@ -176,7 +176,7 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
                         density_percentile_threshold=10.0, point_radius_estimation_knn=24,
                         octree_max_depth=21, contouring_value_threshold=1.0,
                         keep_n_connected_components=2**63 - 1, minimum_component_size=3, *, weights=None,
-                        precision="f32", vertex_normals=False, point_attributes=None):
+                        precision="f32", vertex_normals=False, point_attributes=None, simplify=0):
     """module.cpp:58-109,291-346 -> asr::ReconstructSurface (cpp/lib/asr.cpp:95-349): pre-filter,
     implicit values, dual contouring, component filter; every stage on the MI355X.
     `weights` (keyword only) replaces the reference's bundled model.pt, see _load_weights.
@@ -187,8 +187,14 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
     network's field at every final vertex (ImplicitPipeline.query), zero where the gradient vanishes.
     `point_attributes` (keyword only): f32-convertible [num_points] or [num_points, C], e.g. the colours of the scan;
     the result then holds "vertex_attributes" f32 [V,C], the attributes of the inlier points blended at every final
-    vertex at the scale of the leaf that contains it (ImplicitPipeline.transfer), 0 where no point is near."""
+    vertex at the scale of the leaf that contains it (ImplicitPipeline.transfer), 0 where no point is near.
+    `simplify` (keyword only): k > 0 merges, after the component filter, all vertices inside one octree cell k levels
+    above the leaf that contains them and places the merged vertex on the planes of the triangles around it
+    (ImplicitPipeline.mesh); it runs before vertex_normals and point_attributes, which describe the final vertices."""
     from asr_hip.pipeline import ImplicitPipeline
+    simplify = int(simplify)
+    if simplify < 0:
+        raise ValueError("simplify must be >= 0")
     if precision not in _lib.PRECISIONS:
         raise ValueError("precision must be one of %s" % ", ".join(sorted(_lib.PRECISIONS)))
     points = _f32(points, "points", "[num_points,3]", 2, 3)
@@ -234,7 +240,8 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
     bb_min, bb_max = points.min(0), points.max(0)
     points_dev, radii_dev = torch.from_numpy(points).to(dev), torch.from_numpy(radii).to(dev)
     pipe.forward(points_dev, torch.from_numpy(normals).to(dev), radii_dev, bb_min, bb_max)
-    v, t = pipe.mesh(contouring_value_threshold, keep_n_connected_components, minimum_component_size)
+    v, t = pipe.mesh(contouring_value_threshold, keep_n_connected_components, minimum_component_size,
+                     **({"simplify": simplify} if simplify else {}))
     result = {"vertices": v.cpu().numpy(), "triangles": t.cpu().numpy()}
     if vertex_normals:
         _, grad = pipe.query(v, gradient=True)
@@ -266,6 +273,47 @@ def remove_connected_components(vertices, triangles, keep_n_largest_components,
     return {"vertices": v.cpu().numpy(), "triangles": t.cpu().numpy()}
 
 
+def _margin_frame(points):
+    """the octree frame around points [N,3]: their bounding box and a margin of a thousandth of its longest side"""
+    lo, hi = points.min(0), points.max(0)
+    m = max(1e-3, 1e-3 * float((hi - lo).max()))
+    return _lib.frame_init(lo - np.float32(m), hi + np.float32(m))
+
+
+def simplify_mesh(vertices, triangles, cell_size, return_map=False):
+    """Not in the reference's module.  Simplifies any triangle mesh by octree vertex clustering with quadric placement
+    (asr_hip.ops.mesh_simplify): all vertices inside one cell of a regular grid become one vertex, placed on the planes
+    of the triangles around it and kept inside the cell; triangles that collapse or repeat are dropped.  The grid is a
+    level of the octree frame around the mesh's bounding box (with KDTree's margin): the deepest level whose voxel size
+    is >= cell_size.  THE CELL ACTUALLY USED IS THAT VOXEL SIZE, between cell_size and twice cell_size (the root cube
+    when cell_size exceeds it); it is returned as "cell_size".  The result may have non-manifold edges.
+    -> {'vertices': f32 [V',3], 'triangles': i32 [T',3], 'cell_size': float, 'level': int}; return_map=True adds
+    'vertex_map': int32 [V], the output vertex of every input vertex or -1."""
+    vertices = _f32(vertices, "vertices", "[V,3]", 2, 3)
+    triangles = np.ascontiguousarray(triangles, dtype=np.int32)
+    if triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError("triangles must have shape [T,3]")
+    cell_size = float(cell_size)
+    if not (np.isfinite(cell_size) and cell_size > 0):
+        raise ValueError("cell_size must be a positive number")
+    if vertices.shape[0] == 0:
+        raise ValueError("the mesh has no vertices")
+    if not np.isfinite(vertices).all():
+        raise ValueError("vertices must be finite")
+    frame = _margin_frame(vertices)
+    level = 0
+    while level < _lib.ASR_MAX_LEVEL and frame.voxel_size[level + 1] >= cell_size:
+        level += 1
+    dev = torch.device("cuda")
+    out = _ops.mesh_simplify(frame, torch.from_numpy(vertices).to(dev), torch.from_numpy(triangles).to(dev), level=level,
+                             return_map=True)
+    result = {"vertices": out[0].cpu().numpy(), "triangles": out[1].cpu().numpy(),
+              "cell_size": float(frame.voxel_size[level]), "level": level}
+    if return_map:
+        result["vertex_map"] = out[2].cpu().numpy()
+    return result
+
+
 class KDTree:
     """cpp/pybind/module.cpp:237-277,455-489 -> asr::KDTree (cpp/lib/nsearch.cpp:23-105).  The
     reference builds a nanoflann tree; here the points are Morton sorted on the GPU and all three
@@ -276,9 +324,7 @@ class KDTree:
         if points.ndim != 2 or points.shape[1] != 3:
             raise ValueError("points must have shape [N,3]")
         self._points = torch.from_numpy(points).to(torch.device("cuda"))
-        lo, hi = points.min(0), points.max(0)
-        m = max(1e-3, 1e-3 * float((hi - lo).max()))
-        self._frame = _lib.frame_init(lo - np.float32(m), hi + np.float32(m))
+        self._frame = _margin_frame(points)
 
     def compute_k_radius(self, k):
         return _ops.knn_radius(self._frame, self._points, k).cpu().numpy()

@@ -152,6 +152,7 @@ EXPORTS = [
     "asr_hip_aggregation_importance", "asr_hip_sparse_conv_f32", "asr_hip_invert_neighbors_list", "asr_hip_row_groups",
     "asr_hip_reduce_subarrays_sum", "asr_hip_decode_mlp", "asr_hip_leaf_locate", "asr_hip_decode_mlp_at",
     "asr_hip_point_attributes_at", "asr_hip_nearest_point", "asr_hip_mesh_sample",
+    "asr_hip_mesh_simplify_count", "asr_hip_mesh_simplify_fill",
     "asr_hip_implicit_build",
     "asr_hip_implicit_network", "asr_hip_implicit_aggregate", "asr_hip_implicit_forward", "asr_hip_implicit_get",
     "asr_hip_implicit_stage_ms", "asr_hip_implicit_query",
@@ -192,6 +193,11 @@ def load():
         lib.asr_hip_nearest_point.restype = ctypes.c_int
         lib.asr_hip_mesh_sample.argtypes = [vp, vp, i64, vp, i64, i64, ctypes.c_uint64, vp, vp, vp]
         lib.asr_hip_mesh_sample.restype = ctypes.c_int
+        lib.asr_hip_mesh_simplify_count.argtypes = [vp, ctypes.POINTER(OctreeFrame), vp, i64, vp, i64, vp, ctypes.c_int,
+                                                    ctypes.POINTER(i64), ctypes.POINTER(i64)]
+        lib.asr_hip_mesh_simplify_count.restype = ctypes.c_int
+        lib.asr_hip_mesh_simplify_fill.argtypes = [vp, vp, vp, vp]
+        lib.asr_hip_mesh_simplify_fill.restype = ctypes.c_int
         _lib = lib
     return _lib
 

@@ -681,6 +681,39 @@ def mesh_sample(vertices, triangles, num_samples, seed=0, normals=False, return_
     return out[0] if len(out) == 1 else out
 
 
+def mesh_simplify(frame, vertices, triangles, level=None, levels=None, return_map=False, ctx=None):
+    """Octree vertex clustering with quadric placement (asr_hip_mesh_simplify_count / _fill; the contract is in
+    include/asr_hip.h): all vertices in one cell of `frame` at `level` (0..21, one for the whole mesh) or at `levels`
+    (int8-convertible [V], one per vertex) become one vertex, placed on the planes of the triangles around it and kept
+    inside the cell; triangles that collapse or repeat are dropped.  Exactly one of level and levels must be given.
+    -> (vertices f32 [V',3], triangles int32 [T',3]); return_map=True adds vertex_map int32 [V], the output vertex of
+    every input vertex or -1.  The result may have non-manifold edges; it is not filtered (remove_components)."""
+    vertices = _dev(vertices, torch.float32)
+    triangles = _dev(triangles, torch.int32)
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must have shape [V,3]")
+    if triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError("triangles must have shape [T,3]")
+    if (level is None) == (levels is None):
+        raise ValueError("give exactly one of level and levels")
+    nv = vertices.shape[0]
+    if levels is not None:
+        levels = _dev(levels, torch.int8)
+        if tuple(levels.shape) != (nv,):
+            raise ValueError("levels must have shape [V]")
+    dev = _same_device(vertices, triangles, levels)
+    ctx = ctx or context(dev)
+    nvo, nto = i64(0), i64(0)
+    ctx.call("asr_hip_mesh_simplify_count", ctypes.byref(frame), ptr(vertices), i64(nv), ptr(triangles),
+             i64(triangles.shape[0]), ptr(levels), int(level) if levels is None else 0, ctypes.byref(nvo),
+             ctypes.byref(nto))
+    v2 = torch.empty((nvo.value, 3), dtype=torch.float32, device=dev)
+    t2 = torch.empty((nto.value, 3), dtype=torch.int32, device=dev)
+    vmap = torch.empty(nv, dtype=torch.int32, device=dev) if return_map else None
+    ctx.call("asr_hip_mesh_simplify_fill", ptr(v2), ptr(t2), ptr(vmap))
+    return (v2, t2, vmap) if return_map else (v2, t2)
+
+
 def decode_mlp_at(code, shifts, w1, b1, w2, b2, w3, rows=None, voxel_sizes=None, gradient=False):
     """UNet5.decode(shifts, code[rows]) (net_definitions_torch.py:655-666) -> values [M,2]; with gradient=True
     (values, grad [M,3]) where grad is decode_with_gradient's d values[:,0] / d shift (:668-686, unscaled).

@@ -249,16 +249,41 @@ class ImplicitPipeline:
         return ops.dual_cells(self.device, ctx=self.ctx)
 
     def mesh(self, contouring_value_threshold=1.0, keep_n_connected_components=2**63 - 1,
-             minimum_component_size=3, values=None):
+             minimum_component_size=3, values=None, simplify=0):
         """contouring + component filter on the last forward (cpp/lib/asr.cpp:338-346) ->
-        (vertices f32[M,3], triangles i32[T,3]) on the GPU"""
+        (vertices f32[M,3], triangles i32[T,3]) on the GPU.  simplify=k > 0 (not in the reference): the filtered mesh
+        is then simplified in the forward's frame (ops.mesh_simplify): all vertices inside one cell k levels above the
+        grid-0 leaf that contains them become one vertex (level max(0, leaf level - k); a vertex outside every leaf
+        stays alone).  The simplified mesh is not filtered again."""
         from . import ops
         self._stream()
         if values is None:
             values = self.get("values")
         duals = ops.dual_cells(self.device, ctx=self.ctx)
         v, t = ops.contour(values, duals, self.get("voxel_centers0"), contouring_value_threshold, ctx=self.ctx)
-        return ops.remove_components(v, t, keep_n_connected_components, minimum_component_size, ctx=self.ctx)
+        v, t = ops.remove_components(v, t, keep_n_connected_components, minimum_component_size, ctx=self.ctx)
+        k = int(simplify)
+        if k < 0:
+            raise ValueError("simplify must be >= 0")
+        if k == 0:
+            return v, t
+        frame = _lib.frame_init(*self._bb)
+        with torch.cuda.device(self.device):
+            return ops.mesh_simplify(frame, v, t, levels=self.simplify_levels(v, k), ctx=self.ctx)
+
+    def simplify_levels(self, vertices, k):
+        """int8 [V]: max(0, level of the grid-0 leaf that contains each vertex - k); 21 where no leaf does"""
+        from . import ops
+        frame = _lib.frame_init(*self._bb)
+        keys = self.get("voxel_keys0")
+        with torch.cuda.device(self.device):
+            rows = ops.leaf_locate(frame, keys, vertices).long()
+        # level of a location code = index of its marker bit / 3 = how many of key >> 3, key >> 6, ... are not zero (the
+        # codes are uint64 bit patterns in int64: the shift of a level-21 code, which is negative, drags its sign along)
+        leaf_level = sum(((keys >> (3 * l)) != 0).long() for l in range(1, _lib.ASR_MAX_LEVEL + 1))
+        lev = leaf_level[rows.clamp(min=0)]
+        lev = torch.where(rows >= 0, (lev - int(k)).clamp(min=0), torch.full_like(lev, _lib.ASR_MAX_LEVEL))
+        return lev.to(torch.int8)
 
     def stage_ms(self):
         ms = (ctypes.c_float * 8)()

@@ -212,6 +212,21 @@ def read_mesh(path, with_normals=False, with_colors=False):
     return out
 
 
+def average_colors(colors, vertex_map, num_out):
+    """colours uint8 [V,3] of a mesh carried through the vertex_map int [V] of a simplification (-1: the vertex is
+    gone): every output vertex gets the mean of the colours mapped onto it, rounded to nearest; an output vertex that
+    nothing maps to is black -> uint8 [num_out,3]"""
+    c = _check_colors(colors, len(vertex_map), "vertex").astype(np.float64)
+    vm = np.asarray(vertex_map, np.int64)
+    keep = vm >= 0
+    if keep.any() and vm.max() >= num_out:
+        raise ValueError("vertex_map points past the output vertices")
+    total = np.zeros((num_out, 3))
+    np.add.at(total, vm[keep], c[keep])
+    count = np.bincount(vm[keep], minlength=num_out)[:, None]
+    return np.rint(total / np.maximum(count, 1)).astype(np.uint8)
+
+
 def read_surface(path):
     """A surface to compare against (asrtool --compare): -> (vertices f32 [N,3], triangles i32 [T,3] or None, normals
     f32 [N,3] or None).  A file with a non-empty face element is a triangle mesh in the layout write_mesh produces; one

@@ -709,6 +709,23 @@ int asr_hip_mesh_sample(asr_hip_context* ctx, const float* vertices, int64_t num
     return asr_mesh_sample(ctx, vertices, num_vertices, triangles, num_triangles, num_samples, seed, points_out,
                            normals_out, triangle_out);
 }
+int asr_hip_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* frame, const float* vertices,
+                                int64_t num_vertices, const int32_t* triangles, int64_t num_triangles, const int8_t* levels,
+                                int level, int64_t* num_vertices_out, int64_t* num_triangles_out) {
+    CTX_GUARD(ctx);
+    if (!frame || !num_vertices_out || !num_triangles_out || (num_vertices > 0 && !vertices) ||
+        (num_triangles > 0 && !triangles))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify_count: null argument");
+    if (num_vertices < 0 || num_triangles < 0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify_count: negative size");
+    if (num_vertices >= (i64(1) << 31) || num_triangles >= (i64(1) << 31) / 3)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify_count: mesh does not fit 32-bit indices");
+    return asr_mesh_simplify_count(ctx, frame, vertices, num_vertices, triangles, num_triangles, levels, level,
+                                   num_vertices_out, num_triangles_out);
+}
+int asr_hip_mesh_simplify_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out, int32_t* vertex_map_out) {
+    CTX_GUARD(ctx);
+    return asr_mesh_simplify_fill(ctx, vertices_out, triangles_out, vertex_map_out);
+}
 
 }  // extern "C"
 

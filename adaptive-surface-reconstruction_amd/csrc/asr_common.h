@@ -505,6 +505,10 @@ int asr_mesh_components_fill(asr_hip_context* ctx, float* vertices_out, int32_t*
 // stratified area-weighted samples of a triangle mesh (asr_hip_mesh_sample); normals / tri may be null
 int asr_mesh_sample(asr_hip_context* ctx, const float* vertices, i64 nv, const int32_t* triangles, i64 nt, i64 num_samples,
                     u64 seed, float* points, float* normals, int32_t* tri);
+// octree vertex clustering with quadric placement (asr_hip_mesh_simplify_count / _fill); levels / vertex_map may be null
+int asr_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* frame, const float* vertices, i64 nv,
+                            const int32_t* triangles, i64 nt, const int8_t* levels, int level, i64* nv_out, i64* nt_out);
+int asr_mesh_simplify_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out, int32_t* vertex_map);
 void asr_mesh_release(asr_hip_context* ctx);
 
 int asr_conv_agg_importance(asr_hip_context* ctx, const float* compat, const float* dist, i64 n,

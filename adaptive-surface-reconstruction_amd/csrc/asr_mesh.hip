@@ -28,7 +28,7 @@ __constant__ int c_cube_faces[6][4] = {{0, 1, 3, 2}, {4, 6, 7, 5}, {1, 5, 7, 3},
 __constant__ int c_owned_edges[3][2] = {{0, 1}, {1, 3}, {1, 5}};  // edge subset {0,1,9}
 
 struct MeshState {
-    int kind = 0;  // 1 = contour, 2 = components
+    int kind = 0;  // 1 = contour, 2 = components, 3 = simplify
     // contour
     const float* values = nullptr;
     const i64* duals = nullptr;
@@ -46,6 +46,11 @@ struct MeshState {
     i64 nv = 0, nt = 0, nv_out = 0, nt_out = 0;
     i64* v_off = nullptr;  // exclusive scan of the vertex keep flags (nv+1)
     i64* t_off = nullptr;  // same for triangles
+    // simplify (in_tri, nv, nt, nv_out, nt_out, t_off as above)
+    i64 nc = 0;                       // clusters
+    const int32_t* cluster = nullptr;  // vertex -> cluster
+    const float* cpos = nullptr;      // [nc,3] position of every cluster
+    i64* c_off = nullptr;             // exclusive scan of the clusters a surviving triangle references (nc+1)
 };
 
 __device__ inline bool crossing(const float* values, float thr, i64 a, i64 b) {  // :81-111
@@ -499,6 +504,224 @@ __global__ void k_mesh_sample(const float* __restrict__ vtx, const int32_t* __re
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// asr_hip_mesh_simplify: octree vertex clustering with quadric placement (contract: include/asr_hip.h).
+//   keys      one thread per vertex: key of its cell, checks of the level and of the position
+//   clusters  stable radix sort of (key, vertex); run heads + scan give the cluster ids in ascending key order
+//   corners   (cluster, 3t + j) pairs, stable radix sort: the corners of a cluster are one segment in ascending 3t + j
+//   solve     one wave per cluster: lane l takes the items l, l + 64, ... of the vertex and of the corner segment in
+//             order, a xor butterfly adds the 64 partial sums (a + b == b + a: every lane ends with the same bits), the
+//             3x3 system is solved with an LDL^T factorisation.  No atomics: the same bits on every run.
+//   triangles two stable sort passes over the sorted cluster triple (largest id, then the other two as one key) with the
+//             input index as payload: equal triples become runs in ascending input index, the run heads survive
+//   compact   scans of the survivor flags and of the referenced clusters
+// ------------------------------------------------------------------------------------------
+__global__ void k_simp_keys(asr_octree_frame f, const float* vtx, i64 nv, const int8_t* levels, int level, u64* keys,
+                            int32_t* ids, int* flags) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    const int l = levels ? (int)levels[i] : level;
+    int x = 0, y = 0, z = 0;
+    u64 key = 1;  // the root: what a refused vertex gets (the call fails before anything reads it)
+    if (l < 0 || l > ASR_MAX_LEVEL) {
+        atomicOr(&flags[5], 1);
+    } else if (!frame_coord21_checked(f, vtx[3 * i], vtx[3 * i + 1], vtx[3 * i + 2], x, y, z)) {
+        atomicOr(&flags[6], 1);
+    } else {
+        const int s = ASR_MAX_LEVEL - l;
+        key = asr_coord_key(x >> s, y >> s, z >> s, l);
+    }
+    keys[i] = key;
+    ids[i] = (int32_t)i;
+}
+__global__ void k_simp_heads(const u64* keys, i64 n, i64* head) {
+    const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > n) return;
+    head[r] = (r < n && (r == 0 || keys[r] != keys[r - 1])) ? 1 : 0;
+}
+// hoff: exclusive scan of the head flags; position r of the sorted list lies in cluster hoff[r + 1] - 1
+__global__ void k_simp_clusters(const u64* keys, const int32_t* ids, i64 n, const i64* hoff, int32_t* cluster,
+                                u64* ckey, i64* cstart) {
+    const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > n) return;
+    if (r == n) {
+        cstart[hoff[n]] = n;
+        return;
+    }
+    const i64 c = hoff[r + 1] - 1;
+    cluster[ids[r]] = (int32_t)c;
+    if (hoff[r + 1] != hoff[r]) {
+        ckey[c] = keys[r];
+        cstart[c] = r;
+    }
+}
+__global__ void k_simp_corner_keys(const int32_t* tri, i64 ncorner, i64 nv, const int32_t* cluster, u32* ck, u32* cv,
+                                   int* flags) {
+    const i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= ncorner) return;
+    const int v = tri[q];
+    u32 c = 0;
+    if (v < 0 || v >= nv)
+        atomicOr(&flags[4], 1);
+    else
+        c = (u32)cluster[v];
+    ck[q] = c;
+    cv[q] = (u32)q;
+}
+// kstart[c] = first position of the sorted corner list with cluster >= c (c = 0..nc)
+__global__ void k_simp_corner_starts(const u32* ck, i64 ncorner, i64 nc, i64* kstart) {
+    const i64 c = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c > nc) return;
+    i64 lo = 0, hi = ncorner;
+    while (lo < hi) {
+        const i64 mid = (lo + hi) >> 1;
+        if ((i64)ck[mid] < c)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    kstart[c] = lo;
+}
+__device__ inline double wave_sum(double v) {
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+__global__ void __launch_bounds__(BLK) k_simp_solve(asr_octree_frame f, const float* __restrict__ vtx,
+                                                    const int32_t* __restrict__ tri, const int32_t* __restrict__ ids,
+                                                    const u64* __restrict__ ckey, const i64* __restrict__ cstart,
+                                                    const u32* __restrict__ corner, const i64* __restrict__ kstart,
+                                                    i64 nc, float* __restrict__ cpos) {
+    const i64 c = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (c >= nc) return;  // whole waves leave: the shuffles below see 64 lanes
+    const i64 v0 = cstart[c], v1 = cstart[c + 1];
+    if (v1 - v0 == 1) {  // a vertex alone in its cell keeps its bits
+        if (lane < 3) cpos[3 * c + lane] = vtx[3 * (i64)ids[v0] + lane];
+        return;
+    }
+    int cx, cy, cz, l;
+    asr_key_coord(ckey[c], cx, cy, cz, l);
+    const int s = ASR_MAX_LEVEL - l;
+    const double vs = (double)f.voxel_size[ASR_MAX_LEVEL], half = 0.5 * (double)(i64(1) << s);
+    const double ctr[3] = {((double)((cx << s) - f.offset[0]) + half) * vs,
+                           ((double)((cy << s) - f.offset[1]) + half) * vs,
+                           ((double)((cz << s) - f.offset[2]) + half) * vs};
+    double m[3] = {0, 0, 0}, A[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};  // A: xx xy xz yy yz zz
+    for (i64 r = v0 + lane; r < v1; r += 64) {
+        const i64 v = ids[r];
+        for (int d = 0; d < 3; ++d) m[d] += (double)vtx[3 * v + d] - ctr[d];
+    }
+    for (i64 k = kstart[c] + lane; k < kstart[c + 1]; k += 64) {
+        const i64 t = corner[k] / 3;
+        double p[3][3];
+        for (int j = 0; j < 3; ++j) {
+            const i64 v = tri[3 * t + j];
+            for (int d = 0; d < 3; ++d) p[j][d] = (double)vtx[3 * v + d] - ctr[d];
+        }
+        const double ux = p[1][0] - p[0][0], uy = p[1][1] - p[0][1], uz = p[1][2] - p[0][2];
+        const double wx = p[2][0] - p[0][0], wy = p[2][1] - p[0][1], wz = p[2][2] - p[0][2];
+        const double nx = uy * wz - uz * wy, ny = uz * wx - ux * wz, nz = ux * wy - uy * wx;
+        const double len = sqrt(nx * nx + ny * ny + nz * nz);
+        if (!(len > 0.0)) continue;
+        const double w = 2.0 * len, d = -(nx * p[0][0] + ny * p[0][1] + nz * p[0][2]);
+        A[0] += nx * nx / w;
+        A[1] += nx * ny / w;
+        A[2] += nx * nz / w;
+        A[3] += ny * ny / w;
+        A[4] += ny * nz / w;
+        A[5] += nz * nz / w;
+        b[0] += d * nx / w;
+        b[1] += d * ny / w;
+        b[2] += d * nz / w;
+    }
+    for (int d = 0; d < 3; ++d) m[d] = wave_sum(m[d]) / (double)(v1 - v0);
+    for (int d = 0; d < 6; ++d) A[d] = wave_sum(A[d]);
+    for (int d = 0; d < 3; ++d) b[d] = wave_sum(b[d]);
+    double x[3] = {m[0], m[1], m[2]};
+    const double trA = A[0] + A[3] + A[5];
+    if (trA > 0.0) {
+        const double eps = 1e-3 * trA / 3.0;
+        const double r0 = -b[0] + eps * m[0], r1 = -b[1] + eps * m[1], r2 = -b[2] + eps * m[2];
+        // (A + eps I) = L D L^T, symmetric positive definite
+        const double d0 = A[0] + eps, l10 = A[1] / d0, l20 = A[2] / d0;
+        const double d1 = (A[3] + eps) - l10 * A[1];
+        const double e21 = A[4] - l20 * A[1], l21 = e21 / d1;
+        const double d2 = (A[5] + eps) - l20 * A[2] - l21 * e21;
+        const double y0 = r0, y1 = r1 - l10 * y0, y2 = r2 - l20 * y0 - l21 * y1;
+        x[2] = y2 / d2;
+        x[1] = y1 / d1 - l21 * x[2];
+        x[0] = y0 / d0 - l10 * x[1] - l20 * x[2];
+    }
+    const double hh = 0.5 * (double)f.voxel_size[l];
+    if (lane < 3) {
+        double xv = lane == 0 ? x[0] : lane == 1 ? x[1] : x[2];
+        const double cv = lane == 0 ? ctr[0] : lane == 1 ? ctr[1] : ctr[2];
+        xv = xv < -hh ? -hh : xv > hh ? hh : xv;
+        cpos[3 * c + lane] = (float)(cv + xv);
+    }
+}
+// sorted cluster triple of every triangle: hi[t] (pass one's key), lomid[t] = lo << bits | mid; degenerate[t]
+__global__ void k_simp_triples(const int32_t* tri, i64 nt, const int32_t* cluster, int bits, u32* hi, u64* lomid,
+                               u32* tid) {
+    const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nt) return;
+    u32 a = (u32)cluster[tri[3 * t]], b = (u32)cluster[tri[3 * t + 1]], c = (u32)cluster[tri[3 * t + 2]];
+    if (a > b) { const u32 s = a; a = b; b = s; }
+    if (b > c) { const u32 s = b; b = c; c = s; }
+    if (a > b) { const u32 s = a; a = b; b = s; }
+    hi[t] = c;
+    lomid[t] = ((u64)a << bits) | (u64)b;
+    tid[t] = (u32)t;
+}
+__global__ void k_simp_gather_lomid(const u64* lomid, const u32* order, i64 nt, u64* out) {
+    const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < nt) out[r] = lomid[order[r]];
+}
+// order: triangles sorted on their triple, equal triples in ascending input index; the head of a run survives unless
+// two of its corners share a cluster
+__global__ void k_simp_survivors(const u32* order, const u64* lomid_sorted, const u32* hi, i64 nt, int bits, i64* flag) {
+    const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > nt) return;
+    if (r == nt) {
+        flag[nt] = 0;
+        return;
+    }
+    const u32 t = order[r];
+    const u64 lm = lomid_sorted[r];
+    const u32 c = hi[t], a = (u32)(lm >> bits), b = (u32)(lm & ((u64(1) << bits) - 1));
+    bool head = r == 0 || lomid_sorted[r - 1] != lm || hi[order[r - 1]] != c;
+    flag[t] = (head && a != b && b != c) ? 1 : 0;
+}
+__global__ void k_simp_mark(const int32_t* tri, i64 nt, const i64* toff, const int32_t* cluster, i64* cref) {
+    const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nt || toff[t + 1] == toff[t]) return;
+    for (int j = 0; j < 3; ++j) cref[cluster[tri[3 * t + j]]] = 1;  // every writer stores the same value
+}
+__global__ void k_simp_out_vertices(const float* cpos, i64 nc, const i64* coff, float* out) {
+    const i64 c = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nc || coff[c + 1] == coff[c]) return;
+    const i64 o = coff[c];
+    for (int d = 0; d < 3; ++d) out[3 * o + d] = cpos[3 * c + d];
+}
+__global__ void k_simp_out_triangles(const int32_t* tri, i64 nt, const i64* toff, const int32_t* cluster,
+                                     const i64* coff, int32_t* out) {
+    const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nt || toff[t + 1] == toff[t]) return;
+    const i64 o = toff[t];
+    for (int j = 0; j < 3; ++j) out[3 * o + j] = (int32_t)coff[cluster[tri[3 * t + j]]];
+}
+// cluster == nullptr: no triangle survived, nothing is referenced
+__global__ void k_simp_vertex_map(const int32_t* cluster, const i64* coff, i64 nv, int32_t* map) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    int32_t o = -1;
+    if (cluster) {
+        const i64 c = cluster[i];
+        if (coff[c + 1] != coff[c]) o = (int32_t)coff[c];
+    }
+    map[i] = o;
+}
+
 MeshState& mstate(asr_hip_context* ctx) {
     if (!ctx->mesh_state) ctx->mesh_state = new MeshState();
     return *(MeshState*)ctx->mesh_state;
@@ -700,6 +923,137 @@ int asr_mesh_components_fill(asr_hip_context* ctx, float* vertices_out, int32_t*
     if (st.nt > 0 && st.nt_out > 0) {
         k_compact_triangles<<<grid_for(st.nt, BLK), BLK, 0, s>>>(st.in_tri, st.nt, st.v_off, st.t_off,
                                                                  triangles_out);
+        ASR_CHECK_LAUNCH(ctx);
+    }
+    ASR_HIP_CHECK(ctx, hipStreamSynchronize(s));
+    return ASR_HIP_OK;
+}
+
+int asr_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* frame, const float* vertices, i64 nv,
+                            const int32_t* triangles, i64 nt, const int8_t* levels, int level, i64* nv_out, i64* nt_out) {
+    MeshState& st = mstate(ctx);
+    st = MeshState();
+    *nv_out = 0;
+    *nt_out = 0;
+    if (!levels && (level < 0 || level > ASR_MAX_LEVEL))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: level %d is not in 0..%d", level, ASR_MAX_LEVEL);
+    if (nv == 0 && nt == 0) {
+        st.kind = 3;
+        return ASR_HIP_OK;
+    }
+    ASR_TRY(ensure_flags(ctx));
+    ctx->scratch.reset();
+    hipStream_t s = ctx->stream;
+    ASR_TRY(fresh_flags(ctx));
+    const i64 nq = 3 * nt;
+    if (nv == 0)  // every corner is out of range
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: triangle index out of range");
+    MESH_ALLOC(keys, u64, nv);
+    MESH_ALLOC(ids, int32_t, nv);
+    MESH_ALLOC(keys_s, u64, nv);
+    MESH_ALLOC(ids_s, int32_t, nv);
+    MESH_ALLOC(head, i64, nv + 1);
+    MESH_ALLOC(hoff, i64, nv + 1);
+    MESH_ALLOC(cluster, int32_t, nv);
+    MESH_ALLOC(ckey, u64, nv);
+    MESH_ALLOC(cstart, i64, nv + 1);
+    k_simp_keys<<<grid_for(nv, BLK), BLK, 0, s>>>(*frame, vertices, nv, levels, level, keys, ids, ctx->d_flags);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(sort_pairs(ctx, ctx->scratch, keys, keys_s, ids, ids_s, nv, 64));
+    k_simp_heads<<<grid_for(nv + 1, BLK), BLK, 0, s>>>(keys_s, nv, head);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(scan_counts(ctx, ctx->scratch, head, hoff, nv + 1));
+    k_simp_clusters<<<grid_for(nv + 1, BLK), BLK, 0, s>>>(keys_s, ids_s, nv, hoff, cluster, ckey, cstart);
+    ASR_CHECK_LAUNCH(ctx);
+    u32 *ck = nullptr, *cv = nullptr, *ck_s = nullptr, *cv_s = nullptr;
+    if (nt > 0) {
+        ck = arena_alloc<u32>(ctx->scratch, (size_t)nq);
+        cv = arena_alloc<u32>(ctx->scratch, (size_t)nq);
+        ck_s = arena_alloc<u32>(ctx->scratch, (size_t)nq);
+        cv_s = arena_alloc<u32>(ctx->scratch, (size_t)nq);
+        if (!ck || !cv || !ck_s || !cv_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+        k_simp_corner_keys<<<grid_for(nq, BLK), BLK, 0, s>>>(triangles, nq, nv, cluster, ck, cv, ctx->d_flags);
+        ASR_CHECK_LAUNCH(ctx);
+    }
+    i64 nc = 0;
+    int host[16];
+    ASR_TRY(read_i64(ctx, hoff + nv, &nc));
+    ASR_TRY(read_flags(ctx, host));
+    // nothing below runs on a refused mesh: the kernels that follow index with the corners and shift by the levels
+    if (host[5]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: a vertex level is not in 0..%d", ASR_MAX_LEVEL);
+    if (host[6]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: vertex outside the frame (or not finite)");
+    if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: triangle index out of range");
+    st.nv = nv;
+    if (nt == 0) {  // no triangle: no output vertex, vertex_map is all -1
+        st.kind = 3;
+        return ASR_HIP_OK;
+    }
+    const int bits = bits_for(nc);
+    ASR_TRY(sort_pairs(ctx, ctx->scratch, ck, ck_s, cv, cv_s, nq, bits));
+    MESH_ALLOC(kstart, i64, nc + 1);
+    MESH_ALLOC(cpos, float, nc * 3);
+    k_simp_corner_starts<<<grid_for(nc + 1, BLK), BLK, 0, s>>>(ck_s, nq, nc, kstart);
+    ASR_CHECK_LAUNCH(ctx);
+    k_simp_solve<<<grid_for(nc * 64, BLK), BLK, 0, s>>>(*frame, vertices, triangles, ids_s, ckey, cstart, cv_s, kstart,
+                                                        nc, cpos);
+    ASR_CHECK_LAUNCH(ctx);
+    // duplicates: the corner buffers are free again (same sizes: 3 nt u32 each)
+    u32 *hi = ck, *tid = cv, *tid1 = cv_s, *hi_s = ck_s;
+    MESH_ALLOC(lomid, u64, nt);
+    MESH_ALLOC(lomid1, u64, nt);
+    MESH_ALLOC(lomid2, u64, nt);
+    MESH_ALLOC(tid2, u32, nt);
+    MESH_ALLOC(tflag, i64, nt + 1);
+    MESH_ALLOC(toff, i64, nt + 1);
+    MESH_ALLOC(cref, i64, nc + 1);
+    MESH_ALLOC(coff, i64, nc + 1);
+    k_simp_triples<<<grid_for(nt, BLK), BLK, 0, s>>>(triangles, nt, cluster, bits, hi, lomid, tid);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(sort_pairs(ctx, ctx->scratch, hi, hi_s, tid, tid1, nt, bits));
+    k_simp_gather_lomid<<<grid_for(nt, BLK), BLK, 0, s>>>(lomid, tid1, nt, lomid1);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(sort_pairs(ctx, ctx->scratch, lomid1, lomid2, tid1, tid2, nt, 2 * bits));
+    k_simp_survivors<<<grid_for(nt + 1, BLK), BLK, 0, s>>>(tid2, lomid2, hi, nt, bits, tflag);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(scan_counts(ctx, ctx->scratch, tflag, toff, nt + 1));
+    ASR_HIP_CHECK(ctx, hipMemsetAsync(cref, 0, (size_t)(nc + 1) * sizeof(i64), s));
+    k_simp_mark<<<grid_for(nt, BLK), BLK, 0, s>>>(triangles, nt, toff, cluster, cref);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(scan_counts(ctx, ctx->scratch, cref, coff, nc + 1));
+    i64 sizes[2] = {0, 0};
+    ASR_HIP_CHECK(ctx, hipMemcpyAsync(&sizes[0], coff + nc, sizeof(i64), hipMemcpyDeviceToHost, s));
+    ASR_HIP_CHECK(ctx, hipMemcpyAsync(&sizes[1], toff + nt, sizeof(i64), hipMemcpyDeviceToHost, s));
+    ASR_HIP_CHECK(ctx, hipStreamSynchronize(s));
+    st.kind = 3;
+    st.in_tri = triangles;
+    st.nt = nt;
+    st.nc = nc;
+    st.cluster = cluster;
+    st.cpos = cpos;
+    st.c_off = coff;
+    st.t_off = toff;
+    st.nv_out = *nv_out = sizes[0];
+    st.nt_out = *nt_out = sizes[1];
+    return ASR_HIP_OK;
+}
+
+int asr_mesh_simplify_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out, int32_t* vertex_map) {
+    MeshState& st = mstate(ctx);
+    if (st.kind != 3)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify_fill must follow the matching mesh_simplify_count call");
+    st.kind = 0;
+    hipStream_t s = ctx->stream;
+    if (st.nv_out > 0) {
+        k_simp_out_vertices<<<grid_for(st.nc, BLK), BLK, 0, s>>>(st.cpos, st.nc, st.c_off, vertices_out);
+        ASR_CHECK_LAUNCH(ctx);
+    }
+    if (st.nt_out > 0) {
+        k_simp_out_triangles<<<grid_for(st.nt, BLK), BLK, 0, s>>>(st.in_tri, st.nt, st.t_off, st.cluster, st.c_off,
+                                                                  triangles_out);
+        ASR_CHECK_LAUNCH(ctx);
+    }
+    if (vertex_map && st.nv > 0) {
+        k_simp_vertex_map<<<grid_for(st.nv, BLK), BLK, 0, s>>>(st.cluster, st.c_off, st.nv, vertex_map);
         ASR_CHECK_LAUNCH(ctx);
     }
     ASR_HIP_CHECK(ctx, hipStreamSynchronize(s));

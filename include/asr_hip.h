@@ -481,6 +481,42 @@ int asr_hip_nearest_point(asr_hip_context* ctx, const asr_octree_frame* frame, c
 int asr_hip_mesh_sample(asr_hip_context* ctx, const float* vertices_dev, int64_t num_vertices,
                         const int32_t* triangles_dev, int64_t num_triangles, int64_t num_samples, uint64_t seed,
                         float* points_out_dev, float* normals_out_dev, int32_t* triangle_out_dev);
+/* ---- mesh simplification: octree vertex clustering with quadric placement (not in the reference).
+ * Merges all vertices that share a cell of the frame's octree and places the merged vertex on the planes of the
+ * triangles around it.  Count / fill pair like asr_hip_components_*; the contract, which tests/mesh_simplify_ref.py
+ * restates in numpy:
+ *   Cell of vertex i: its level is l_i = levels_dev[i], or `level` when levels_dev is NULL, and must lie in
+ *     0..ASR_MAX_LEVEL (else ASR_HIP_EINVAL).  With c21 = floor(p * inv_voxel_size[21]) + offset per axis (f32, as in
+ *     asr_hip_leaf_locate) the cell is c21 >> (21 - l_i) and its key the location code of (cell, l_i).  A vertex that
+ *     is not finite or lies outside the root cube is ASR_HIP_EINVAL ("vertex outside the frame"), a triangle corner
+ *     outside [0, num_vertices) is ASR_HIP_EINVAL ("out of range").
+ *   Clusters: the distinct keys.  Cells of different levels are different clusters, even when one contains the other.
+ *   Triangles: every corner is replaced by its cluster; a triangle with two equal corners is dropped; among the
+ *     triangles with the same SET of three clusters (any orientation) the one with the smallest input index survives,
+ *     with its own corner order; survivors keep the input order.
+ *   Output vertices: the clusters that a surviving triangle references, in ascending key order.  vertex_map[i] is the
+ *     output index of vertex i's cluster, -1 when no surviving triangle references it.
+ *   Position of a cluster: a cluster of exactly one input vertex copies that vertex's bits.  All others, in f64: with
+ *     s = 21 - l the cell centre is c = (((cell << s) - offset) + 0.5 * 2^s) * (double)voxel_size[21], the cell size
+ *     h = voxel_size[l], and all coordinates are taken relative to c.  Every corner (t, j) of every INPUT triangle
+ *     whose corner vertex lies in the cluster (triangles that collapse later too) contributes, with
+ *     N = (p1 - p0) x (p2 - p0) of triangle t and only if |N| > 0:  A += N N^T / (2|N|),  b += -(N . p0) N / (2|N|).
+ *     m is the plain mean of the cluster's vertices.  If tr A > 0: eps = 1e-3 tr(A) / 3 and x solves
+ *     (A + eps I) x = -b + eps m; otherwise x = m.  x is clamped per axis to [-h/2, h/2]; the output is (float)(c + x).
+ *   Determinism: no floating-point atomics; the corners of a cluster are summed in a fixed order and shape, so the
+ *     same inputs give the same bits on every run.
+ * num_vertices == 0 or num_triangles == 0 is valid and gives an empty result (the vertices are still checked).
+ * Sizes < 2^31 vertices and < 2^31 / 3 triangles.  _count reads the cluster count and the error flags back once and
+ * the two output sizes once; scratch comes from the context arena and stays valid until _fill, which must be the next
+ * mesh call on the context.  vertex_map_out_dev [num_vertices] may be NULL.
+ * Clustering can create non-manifold edges and vertices (two sheets closer than a cell merge); the result is not
+ * filtered -- running asr_hip_components_* afterwards is the caller's choice. */
+int asr_hip_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* frame, const float* vertices_dev,
+                                int64_t num_vertices, const int32_t* triangles_dev, int64_t num_triangles,
+                                const int8_t* levels_dev, int level, int64_t* num_vertices_out,
+                                int64_t* num_triangles_out);
+int asr_hip_mesh_simplify_fill(asr_hip_context* ctx, float* vertices_out_dev, int32_t* triangles_out_dev,
+                               int32_t* vertex_map_out_dev);
 /* (asr_hip_implicit_query, the whole-path query on the last forward, is declared after asr_hip_implicit_stage_ms) */
 
 /* ---- whole path: the section of asr::ReconstructSurface between the pre-filter and the
