@@ -176,7 +176,7 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
                         density_percentile_threshold=10.0, point_radius_estimation_knn=24,
                         octree_max_depth=21, contouring_value_threshold=1.0,
                         keep_n_connected_components=2**63 - 1, minimum_component_size=3, *, weights=None,
-                        precision="f32", vertex_normals=False, point_attributes=None, simplify=0):
+                        precision="f32", vertex_normals=False, point_attributes=None, simplify=0, smooth=0):
     """module.cpp:58-109,291-346 -> asr::ReconstructSurface (cpp/lib/asr.cpp:95-349): pre-filter,
     implicit values, dual contouring, component filter; every stage on the MI355X.
     `weights` (keyword only) replaces the reference's bundled model.pt, see _load_weights.
@@ -190,11 +190,17 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
     vertex at the scale of the leaf that contains it (ImplicitPipeline.transfer), 0 where no point is near.
     `simplify` (keyword only): k > 0 merges, after the component filter, all vertices inside one octree cell k levels
     above the leaf that contains them and places the merged vertex on the planes of the triangles around it
-    (ImplicitPipeline.mesh); it runs before vertex_normals and point_attributes, which describe the final vertices."""
+    (ImplicitPipeline.mesh); it runs before vertex_normals and point_attributes, which describe the final vertices.
+    `smooth` (keyword only): n > 0 runs n iterations of Taubin smoothing (asr_hip.ops.mesh_smooth with its defaults:
+    lambda 0.5, mu -0.53, rims smoothed along themselves) after the component filter and after simplify, also before
+    vertex_normals and point_attributes."""
     from asr_hip.pipeline import ImplicitPipeline
     simplify = int(simplify)
     if simplify < 0:
         raise ValueError("simplify must be >= 0")
+    smooth = int(smooth)
+    if not 0 <= smooth <= 1000:
+        raise ValueError("smooth must be a number of iterations in 0..1000")
     if precision not in _lib.PRECISIONS:
         raise ValueError("precision must be one of %s" % ", ".join(sorted(_lib.PRECISIONS)))
     points = _f32(points, "points", "[num_points,3]", 2, 3)
@@ -241,7 +247,7 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
     points_dev, radii_dev = torch.from_numpy(points).to(dev), torch.from_numpy(radii).to(dev)
     pipe.forward(points_dev, torch.from_numpy(normals).to(dev), radii_dev, bb_min, bb_max)
     v, t = pipe.mesh(contouring_value_threshold, keep_n_connected_components, minimum_component_size,
-                     **({"simplify": simplify} if simplify else {}))
+                     **({"simplify": simplify} if simplify else {}), **({"smooth": smooth} if smooth else {}))
     result = {"vertices": v.cpu().numpy(), "triangles": t.cpu().numpy()}
     if vertex_normals:
         _, grad = pipe.query(v, gradient=True)
@@ -312,6 +318,38 @@ def simplify_mesh(vertices, triangles, cell_size, return_map=False):
     if return_map:
         result["vertex_map"] = out[2].cpu().numpy()
     return result
+
+
+def smooth_mesh(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, boundary="along"):
+    """Not in the reference's module.  Taubin smoothing of any triangle mesh (asr_hip.ops.mesh_smooth): `iterations`
+    times a step p += lam (mean of the edge neighbours - p) and the same step with mu < -lam, which undoes the shrinking
+    of the first (mu = 0: plain Laplacian smoothing).  boundary: "free", "pinned" (the ends of boundary and non-manifold
+    edges stay) or "along" (they move along their own rim or seam only).
+    -> {'vertices': f32 [V,3], 'triangles': i32 [T,3]}; the triangles are the input's."""
+    iterations, lam, mu, _ = _ops.check_smooth_arguments(iterations, lam, mu, boundary)
+    vertices = _f32(vertices, "vertices", "[V,3]", 2, 3)
+    triangles = np.ascontiguousarray(triangles, dtype=np.int32)
+    if triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError("triangles must have shape [T,3]")
+    dev = torch.device("cuda")
+    v = _ops.mesh_smooth(torch.from_numpy(vertices).to(dev), torch.from_numpy(triangles).to(dev), iterations, lam, mu,
+                         boundary)
+    return {"vertices": v.cpu().numpy(), "triangles": triangles}
+
+
+def mesh_topology(triangles, num_vertices=None):
+    """Not in the reference's module.  What kind of mesh is this (asr_hip.ops.mesh_topology) -> dict of Python ints and
+    bools: num_vertices, used_vertices, triangles, degenerate_triangles, edges, boundary_edges, nonmanifold_edges,
+    inconsistent_edges, components, boundary_loops, euler, edge_manifold, oriented, watertight, genus (None unless
+    watertight).  num_vertices None: triangles.max() + 1."""
+    triangles = np.ascontiguousarray(triangles, dtype=np.int32)
+    if triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError("triangles must have shape [T,3]")
+    if num_vertices is None:
+        num_vertices = int(triangles.max()) + 1 if triangles.size else 0
+    if int(num_vertices) < 0:
+        raise ValueError("num_vertices must be >= 0")
+    return _ops.mesh_topology(torch.from_numpy(triangles).to(torch.device("cuda")), int(num_vertices))
 
 
 class KDTree:

@@ -714,6 +714,105 @@ def mesh_simplify(frame, vertices, triangles, level=None, levels=None, return_ma
     return (v2, t2, vmap) if return_map else (v2, t2)
 
 
+def _triangles(triangles):
+    triangles = _dev(triangles, torch.int32)
+    if triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError("triangles must have shape [T,3]")
+    return triangles
+
+
+def _num_vertices(num_vertices):
+    nv = int(num_vertices)
+    if nv < 0:
+        raise ValueError("num_vertices must be >= 0")
+    return nv
+
+
+def mesh_edges(triangles, num_vertices, ctx=None):
+    """The edge table of a triangle list (asr_hip_mesh_edges_count / _fill; the contract is in include/asr_hip.h): the
+    distinct undirected edges (lo, hi) of the triangles with three different corners, in ascending order
+    -> (edges int32 [E,2], uses int32 [E], forward int32 [E]): how many triangle sides use each edge and how many of them
+    run lo -> hi.  uses == 1: boundary, uses >= 3: non-manifold, uses == 2 with forward != 1: inconsistent orientation."""
+    triangles = _triangles(triangles)
+    nv = _num_vertices(num_vertices)
+    dev = triangles.device
+    ctx = ctx or context(dev)
+    ne = i64(0)
+    ctx.call("asr_hip_mesh_edges_count", ptr(triangles), i64(triangles.shape[0]), i64(nv), ctypes.byref(ne))
+    edges = torch.empty((ne.value, 2), dtype=torch.int32, device=dev)
+    uses = torch.empty(ne.value, dtype=torch.int32, device=dev)
+    forward = torch.empty(ne.value, dtype=torch.int32, device=dev)
+    ctx.call("asr_hip_mesh_edges_fill", ptr(edges), ptr(uses), ptr(forward))
+    return edges, uses, forward
+
+
+def topology_summary(counts):
+    """the dict of mesh_topology from the counts of asr_mesh_topology (a dict of ints): adds edge_manifold, oriented,
+    watertight and genus ((2 components - euler) // 2 when watertight, else None).  Host arithmetic only."""
+    out = {k: int(v) for k, v in counts.items()}
+    out["edge_manifold"] = out["nonmanifold_edges"] == 0
+    out["oriented"] = out["inconsistent_edges"] == 0
+    out["watertight"] = (out["boundary_edges"] == 0 and out["nonmanifold_edges"] == 0 and out["inconsistent_edges"] == 0
+                         and out["triangles"] > 0)
+    out["genus"] = (2 * out["components"] - out["euler"]) // 2 if out["watertight"] else None
+    return out
+
+
+def mesh_topology(triangles, num_vertices, ctx=None):
+    """What kind of mesh is this (asr_hip_mesh_topology; definitions in include/asr_hip.h) -> dict of Python ints:
+    num_vertices, used_vertices, triangles, degenerate_triangles, edges, boundary_edges, nonmanifold_edges,
+    inconsistent_edges, components, boundary_loops, euler; and derived from them edge_manifold, oriented, watertight
+    (bools) and genus (int, None unless watertight).  Non-manifold VERTICES are not detected."""
+    triangles = _triangles(triangles)
+    nv = _num_vertices(num_vertices)
+    ctx = ctx or context(triangles.device)
+    out = _lib.MeshTopology()
+    ctx.call("asr_hip_mesh_topology", ptr(triangles), i64(triangles.shape[0]), i64(nv), ctypes.byref(out))
+    return topology_summary({name: getattr(out, name) for name, _ in _lib.MeshTopology._fields_})
+
+
+SMOOTH_BOUNDARY = {"free": 0, "pinned": 1, "along": 2}
+
+
+def check_smooth_arguments(iterations, lam, mu, boundary):
+    """-> (iterations, lam, mu, boundary mode number) or ValueError; no GPU involved"""
+    if isinstance(iterations, bool) or int(iterations) != iterations or not 0 <= int(iterations) <= 1000:
+        raise ValueError("iterations must be an integer in 0..1000")
+    lam, mu = float(lam), float(mu)
+    if not 0.0 < lam <= 1.0:
+        raise ValueError("lam must be in (0, 1]")
+    if not (mu <= 0.0 and mu > float("-inf")):
+        raise ValueError("mu must be a finite number <= 0 (0: plain Laplacian smoothing)")
+    if boundary not in SMOOTH_BOUNDARY:
+        raise ValueError("boundary must be one of %s" % ", ".join(sorted(SMOOTH_BOUNDARY)))
+    return int(iterations), lam, mu, SMOOTH_BOUNDARY[boundary]
+
+
+def mesh_smooth(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, boundary="along", ctx=None, out=None):
+    """Taubin smoothing of a triangle mesh (asr_hip_mesh_smooth; the contract is in include/asr_hip.h): `iterations` times
+    a step p += lam (mean of the edge neighbours - p) followed by the same step with mu < -lam, which undoes the
+    shrinking of the first; mu = 0 is plain Laplacian smoothing.  boundary: "free" (every vertex uses all neighbours),
+    "pinned" (the ends of boundary and non-manifold edges stay where they are) or "along" (they move along their own
+    rim or seam only).  f64 between the steps, one rounding to f32 at the end, the same bits on every run.
+    -> vertices f32 [V,3] (`out`, when given: it may be `vertices` itself); the triangles do not change."""
+    iterations, lam, mu, mode = check_smooth_arguments(iterations, lam, mu, boundary)
+    vertices = _dev(vertices, torch.float32)
+    triangles = _dev(triangles, torch.int32)
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must have shape [V,3]")
+    if triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError("triangles must have shape [T,3]")
+    dev = _same_device(vertices, triangles, out)
+    if out is None:
+        out = torch.empty_like(vertices)
+    elif out.dtype != torch.float32 or out.shape != vertices.shape or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of the shape of vertices")
+    ctx = ctx or context(dev)
+    ctx.call("asr_hip_mesh_smooth", ptr(vertices), i64(vertices.shape[0]), ptr(triangles), i64(triangles.shape[0]),
+             iterations, ctypes.c_double(lam), ctypes.c_double(mu), mode, ptr(out))
+    return out
+
+
 def decode_mlp_at(code, shifts, w1, b1, w2, b2, w3, rows=None, voxel_sizes=None, gradient=False):
     """UNet5.decode(shifts, code[rows]) (net_definitions_torch.py:655-666) -> values [M,2]; with gradient=True
     (values, grad [M,3]) where grad is decode_with_gradient's d values[:,0] / d shift (:668-686, unscaled).

@@ -249,12 +249,13 @@ class ImplicitPipeline:
         return ops.dual_cells(self.device, ctx=self.ctx)
 
     def mesh(self, contouring_value_threshold=1.0, keep_n_connected_components=2**63 - 1,
-             minimum_component_size=3, values=None, simplify=0):
+             minimum_component_size=3, values=None, simplify=0, smooth=0):
         """contouring + component filter on the last forward (cpp/lib/asr.cpp:338-346) ->
         (vertices f32[M,3], triangles i32[T,3]) on the GPU.  simplify=k > 0 (not in the reference): the filtered mesh
         is then simplified in the forward's frame (ops.mesh_simplify): all vertices inside one cell k levels above the
         grid-0 leaf that contains them become one vertex (level max(0, leaf level - k); a vertex outside every leaf
-        stays alone).  The simplified mesh is not filtered again."""
+        stays alone).  The simplified mesh is not filtered again.  smooth=n > 0 (not in the reference): n iterations of
+        Taubin smoothing with the defaults of ops.mesh_smooth, after the component filter and after simplify."""
         from . import ops
         self._stream()
         if values is None:
@@ -262,14 +263,19 @@ class ImplicitPipeline:
         duals = ops.dual_cells(self.device, ctx=self.ctx)
         v, t = ops.contour(values, duals, self.get("voxel_centers0"), contouring_value_threshold, ctx=self.ctx)
         v, t = ops.remove_components(v, t, keep_n_connected_components, minimum_component_size, ctx=self.ctx)
-        k = int(simplify)
+        k, n = int(simplify), int(smooth)
         if k < 0:
             raise ValueError("simplify must be >= 0")
-        if k == 0:
-            return v, t
-        frame = _lib.frame_init(*self._bb)
-        with torch.cuda.device(self.device):
-            return ops.mesh_simplify(frame, v, t, levels=self.simplify_levels(v, k), ctx=self.ctx)
+        if n < 0:
+            raise ValueError("smooth must be >= 0")
+        if k > 0:
+            frame = _lib.frame_init(*self._bb)
+            with torch.cuda.device(self.device):
+                v, t = ops.mesh_simplify(frame, v, t, levels=self.simplify_levels(v, k), ctx=self.ctx)
+        if n > 0:
+            with torch.cuda.device(self.device):
+                v = ops.mesh_smooth(v, t, iterations=n, ctx=self.ctx)
+        return v, t
 
     def simplify_levels(self, vertices, k):
         """int8 [V]: max(0, level of the grid-0 leaf that contains each vertex - k); 21 where no leaf does"""

@@ -3,9 +3,11 @@ reference (cpp/bin/main.cpp:114-177: `asrtool --in point_cloud.ply --out mesh.pl
 `--third-party-notices`) on top of adaptivesurfacereconstruction.reconstruct_surface.
 
     python adaptive-surface-reconstruction_amd/asrtool.py --in scan.ply --out mesh.ply [--weights model.pt] [--precision NAME]
-                                                          [--normals] [--colors] [--simplify K]
+                                                          [--normals] [--colors] [--simplify K] [--smooth N]
     python adaptive-surface-reconstruction_amd/asrtool.py --compare mesh.ply reference.ply [--samples N] [--thresholds a,b,...] [--seed S]
     python adaptive-surface-reconstruction_amd/asrtool.py --decimate mesh.ply out.ply --cell SIZE
+    python adaptive-surface-reconstruction_amd/asrtool.py --smooth-mesh mesh.ply out.ply [--iterations N] [--boundary free|pinned|along]
+    python adaptive-surface-reconstruction_amd/asrtool.py --topology mesh.ply
 
 The reference bundles its network as <resource dir>/model.pt (cpp/lib/asr.cpp:138-139); here the weights come
 from --weights (a TorchScript archive with the same tensor names, a pickled state dict or an .npz) or from
@@ -27,6 +29,16 @@ Options:
     --colors  Carries the input's point colours (red green blue) onto the mesh vertices, blended at each vertex's own scale
     --simplify K  Merges the mesh vertices inside one octree cell K levels above the leaf that contains them (1 <= K <= 21);
               normals and colours then describe the simplified vertices
+    --smooth N  Taubin smoothing of the mesh, N iterations (1 <= N <= 1000), after --simplify; normals and colours then
+              describe the smoothed vertices
+    --smooth-mesh MESH.ply OUT.ply  Instead of reconstructing: Taubin smoothing of an existing mesh (lambda 0.5, mu -0.53).
+              Vertex normals and colours are carried over unchanged
+    --iterations N  --smooth-mesh: iterations (default 10, 0 <= N <= 1000)
+    --boundary MODE  --smooth-mesh: what the vertices of open rims and non-manifold seams do: free (move like all others),
+              pinned (stay) or along (move along their own rim or seam only; default)
+    --topology MESH.ply  Instead of reconstructing: prints one JSON line with the mesh's vertex, triangle and edge counts,
+              boundary / non-manifold / inconsistently oriented edges, components, boundary loops, Euler characteristic,
+              and whether it is edge manifold, oriented and watertight (then also its genus)
     --decimate MESH.ply OUT.ply --cell SIZE  Instead of reconstructing: simplifies an existing mesh by merging the vertices
               inside one cell of a regular grid.  The cell used is the voxel size of the octree level around the mesh that is
               >= SIZE and < 2 SIZE (printed).  Vertex colours are averaged per merged vertex, normals are dropped
@@ -127,6 +139,66 @@ def _decimate(argv):
     return 0
 
 
+def _smooth_mesh(argv):
+    """--smooth-mesh MESH.ply OUT.ply [--iterations N] [--boundary MODE]: 0, or a message on stderr and 1 (before any GPU
+    work) when something is wrong"""
+    i = argv.index("--smooth-mesh")
+    paths = argv[i + 1:i + 3]
+    if len(paths) < 2 or any(p.startswith("--") for p in paths):
+        sys.stderr.write("asrtool: --smooth-mesh needs two files: MESH.ply OUT.ply\n")
+        return 1
+    iterations = 10
+    if "--iterations" in argv:
+        try:
+            iterations = int(_option(argv, "--iterations"))
+        except (TypeError, ValueError):
+            iterations = -1
+        if not 0 <= iterations <= 1000:
+            sys.stderr.write("asrtool: --smooth-mesh: --iterations takes an integer N, 0 <= N <= 1000\n")
+            return 1
+    boundary = "along"
+    if "--boundary" in argv:
+        boundary = _option(argv, "--boundary")
+        if boundary not in ("free", "pinned", "along"):
+            sys.stderr.write("asrtool: --smooth-mesh: --boundary is one of free, pinned, along\n")
+            return 1
+    if not os.path.isfile(paths[0]):
+        sys.stderr.write("asrtool: --smooth-mesh: no such file: %s\n" % paths[0])
+        return 1
+    from asr_hip import ply
+    try:
+        v, t, normals, colors = ply.read_mesh(paths[0], with_normals=True, with_colors=True)
+    except (ValueError, IndexError, OSError) as e:
+        sys.stderr.write("asrtool: --smooth-mesh: cannot read %s as a mesh: %s\n" % (paths[0], e))
+        return 1
+    import adaptivesurfacereconstruction as asr
+    result = asr.smooth_mesh(v, t, iterations=iterations, boundary=boundary)
+    ply.write_mesh(paths[1], result["vertices"], t, normals=normals, colors=colors)
+    print("wrote %s: %d vertices, %d triangles, %d iterations, boundary %s" % (paths[1], len(v), len(t), iterations, boundary))
+    return 0
+
+
+def _topology(argv):
+    """--topology MESH.ply: one JSON line, 0; a message on stderr and 1 (before any GPU work) when something is wrong"""
+    import json
+    path = _option(argv, "--topology")
+    if path is None or path.startswith("--"):
+        sys.stderr.write("asrtool: --topology needs a file: MESH.ply\n")
+        return 1
+    if not os.path.isfile(path):
+        sys.stderr.write("asrtool: --topology: no such file: %s\n" % path)
+        return 1
+    from asr_hip import ply
+    try:
+        v, t = ply.read_mesh(path)
+    except (ValueError, IndexError, OSError) as e:
+        sys.stderr.write("asrtool: --topology: cannot read %s as a mesh: %s\n" % (path, e))
+        return 1
+    import adaptivesurfacereconstruction as asr
+    print(json.dumps(asr.mesh_topology(t, len(v))))
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -142,6 +214,10 @@ def main(argv=None):
         return _compare(argv)
     if "--decimate" in argv:
         return _decimate(argv)
+    if "--smooth-mesh" in argv:
+        return _smooth_mesh(argv)
+    if "--topology" in argv:
+        return _topology(argv)
     inp, out = _option(argv, "--in"), _option(argv, "--out")
     if inp is None or out is None:
         sys.stdout.write(HELP)
@@ -160,6 +236,15 @@ def main(argv=None):
         if not 1 <= simplify <= 21:
             sys.stderr.write("asrtool: --simplify takes a number of octree levels K, 1 <= K <= 21\n")
             return 1
+    smooth = 0
+    if "--smooth" in argv:  # before any GPU work
+        try:
+            smooth = int(_option(argv, "--smooth"))
+        except (TypeError, ValueError):
+            smooth = 0
+        if not 1 <= smooth <= 1000:
+            sys.stderr.write("asrtool: --smooth takes a number of iterations N, 1 <= N <= 1000\n")
+            return 1
     from asr_hip import ply
     colors = None
     if "--colors" in argv:  # before any GPU work: a cloud without colours is an error
@@ -174,6 +259,8 @@ def main(argv=None):
     extra = {} if colors is None else {"point_attributes": colors.astype("float32")}
     if simplify:
         extra["simplify"] = simplify
+    if smooth:
+        extra["smooth"] = smooth
     result = asr.reconstruct_surface(points, normals, radii, weights=_option(argv, "--weights"), precision=precision,
                                      vertex_normals="--normals" in argv, **extra)
     if colors is not None:

@@ -106,6 +106,7 @@ size_t asr_hip_struct_size(const char* name) {
     if (!strcmp(name, "asr_implicit_sizes")) return sizeof(asr_implicit_sizes);
     if (!strcmp(name, "asr_shard_comm")) return sizeof(asr_shard_comm);
     if (!strcmp(name, "asr_shard_stats")) return sizeof(asr_shard_stats);
+    if (!strcmp(name, "asr_mesh_topology")) return sizeof(asr_mesh_topology);
     return 0;
 }
 
@@ -725,6 +726,43 @@ int asr_hip_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* fr
 int asr_hip_mesh_simplify_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out, int32_t* vertex_map_out) {
     CTX_GUARD(ctx);
     return asr_mesh_simplify_fill(ctx, vertices_out, triangles_out, vertex_map_out);
+}
+int asr_hip_mesh_edges_count(asr_hip_context* ctx, const int32_t* triangles, int64_t num_triangles, int64_t num_vertices,
+                             int64_t* num_edges_out) {
+    CTX_GUARD(ctx);
+    if (!num_edges_out || (num_triangles > 0 && !triangles)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_edges_count: null argument");
+    if (num_vertices < 0 || num_triangles < 0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_edges_count: negative size");
+    if (num_vertices >= (i64(1) << 31) || num_triangles >= (i64(1) << 31) / 3)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_edges_count: mesh does not fit 32-bit indices");
+    return asr_mesh_edges_count(ctx, triangles, num_triangles, num_vertices, num_edges_out);
+}
+int asr_hip_mesh_edges_fill(asr_hip_context* ctx, int32_t* edges_out, int32_t* uses_out, int32_t* forward_out) {
+    CTX_GUARD(ctx);
+    return asr_mesh_edges_fill(ctx, edges_out, uses_out, forward_out);
+}
+int asr_hip_mesh_topology(asr_hip_context* ctx, const int32_t* triangles, int64_t num_triangles, int64_t num_vertices,
+                          asr_mesh_topology* out) {
+    CTX_GUARD(ctx);
+    if (!out || (num_triangles > 0 && !triangles)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_topology: null argument");
+    if (num_vertices < 0 || num_triangles < 0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_topology: negative size");
+    if (num_vertices >= (i64(1) << 31) || num_triangles >= (i64(1) << 31) / 3)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_topology: mesh does not fit 32-bit indices");
+    return asr_mesh_topology_report(ctx, triangles, num_triangles, num_vertices, out);
+}
+int asr_hip_mesh_smooth(asr_hip_context* ctx, const float* vertices, int64_t num_vertices, const int32_t* triangles,
+                        int64_t num_triangles, int iterations, double lambda, double mu, int boundary, float* vertices_out) {
+    CTX_GUARD(ctx);
+    if (num_vertices < 0 || num_triangles < 0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: negative size");
+    if (num_vertices >= (i64(1) << 31) || num_triangles >= (i64(1) << 31) / 3)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: mesh does not fit 32-bit indices");
+    if ((num_vertices > 0 && (!vertices || !vertices_out)) || (num_triangles > 0 && !triangles))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: null argument");
+    if (iterations < 0 || iterations > 1000) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: iterations %d is not in 0..1000", iterations);
+    if (!(lambda > 0.0 && lambda <= 1.0)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: lambda %g is not in (0, 1]", lambda);
+    if (!std::isfinite(mu) || mu > 0.0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: mu %g is not a finite number <= 0", mu);
+    if (boundary < 0 || boundary > 2) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: boundary mode %d is not in 0..2", boundary);
+    return asr_mesh_smooth(ctx, vertices, num_vertices, triangles, num_triangles, iterations, lambda, mu, boundary,
+                           vertices_out);
 }
 
 }  // extern "C"

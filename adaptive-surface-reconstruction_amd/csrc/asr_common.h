@@ -509,6 +509,12 @@ int asr_mesh_sample(asr_hip_context* ctx, const float* vertices, i64 nv, const i
 int asr_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* frame, const float* vertices, i64 nv,
                             const int32_t* triangles, i64 nt, const int8_t* levels, int level, i64* nv_out, i64* nt_out);
 int asr_mesh_simplify_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out, int32_t* vertex_map);
+// mesh adjacency (asr_hip_mesh_edges_count / _fill, asr_hip_mesh_topology, asr_hip_mesh_smooth); arguments validated by the callers
+int asr_mesh_edges_count(asr_hip_context* ctx, const int32_t* triangles, i64 nt, i64 nv, i64* num_edges);
+int asr_mesh_edges_fill(asr_hip_context* ctx, int32_t* edges, int32_t* uses, int32_t* forward);
+int asr_mesh_topology_report(asr_hip_context* ctx, const int32_t* triangles, i64 nt, i64 nv, asr_mesh_topology* out);
+int asr_mesh_smooth(asr_hip_context* ctx, const float* vertices, i64 nv, const int32_t* triangles, i64 nt, int iterations,
+                    double lambda, double mu, int boundary, float* vertices_out);
 void asr_mesh_release(asr_hip_context* ctx);
 
 int asr_conv_agg_importance(asr_hip_context* ctx, const float* compat, const float* dist, i64 n,

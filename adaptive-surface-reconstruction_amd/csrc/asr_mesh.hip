@@ -1,4 +1,5 @@
-// asr_mesh.hip -- dual contouring and component filter on the GPU ("next" rows D.2 / D.3).
+// asr_mesh.hip -- dual contouring and component filter on the GPU ("next" rows D.2 / D.3); further down, not in the
+// reference: mesh sampling, simplification and adjacency -- edge table, topology, smoothing (4.9).
 //
 // Replaces asr::CreateTriangleMesh (cpp/lib/contouring.cpp:29-460) and
 // asr::RemoveConnectedComponents (cpp/lib/postprocess.cpp:27-201).  The reference walks the dual
@@ -28,7 +29,7 @@ __constant__ int c_cube_faces[6][4] = {{0, 1, 3, 2}, {4, 6, 7, 5}, {1, 5, 7, 3},
 __constant__ int c_owned_edges[3][2] = {{0, 1}, {1, 3}, {1, 5}};  // edge subset {0,1,9}
 
 struct MeshState {
-    int kind = 0;  // 1 = contour, 2 = components, 3 = simplify
+    int kind = 0;  // 1 = contour, 2 = components, 3 = simplify, 4 = edge table
     // contour
     const float* values = nullptr;
     const i64* duals = nullptr;
@@ -51,6 +52,11 @@ struct MeshState {
     const int32_t* cluster = nullptr;  // vertex -> cluster
     const float* cpos = nullptr;      // [nc,3] position of every cluster
     i64* c_off = nullptr;             // exclusive scan of the clusters a surviving triangle references (nc+1)
+    // edge table
+    i64 num_edges = 0;
+    const u64* e_keys = nullptr;   // sorted side keys
+    const i64* e_start = nullptr;  // first side of every edge (num_edges+1)
+    const i64* e_count = nullptr;  // the number of edges, on the device
 };
 
 __device__ inline bool crossing(const float* values, float thr, i64 a, i64 b) {  // :81-111
@@ -722,6 +728,239 @@ __global__ void k_simp_vertex_map(const int32_t* cluster, const i64* coff, i64 n
     map[i] = o;
 }
 
+// ------------------------------------------------------------------------------------------
+// Mesh adjacency (contract: include/asr_hip.h): edge table, topology report, Taubin smoothing.
+// Every side of a non-degenerate triangle becomes the key (lo << 32) | (hi << 1) | forward; sorted, the runs of equal
+// (lo, hi) are the edges in ascending order and, inside a run, the backward uses come before the forward ones.  The sides
+// of degenerate triangles (and of triangles with a corner out of range, which fail the call) get the key nv << 32 and
+// sort behind every edge.
+// ------------------------------------------------------------------------------------------
+constexpr int SMOOTH_CUT = 128;  // rows longer than this are summed by a whole wave (k_smooth_step_long)
+enum { TOPO_DEGENERATE = 0, TOPO_EDGES, TOPO_BOUNDARY, TOPO_NONMANIFOLD, TOPO_INCONSISTENT, TOPO_USED, TOPO_COMPONENTS,
+       TOPO_LOOPS, TOPO_COUNTERS };
+typedef unsigned long long ull;
+
+// one atomic per wave: the lanes that return early are not active here and are left out of the ballot
+__device__ inline void wave_count(ull* counter, bool pred) {
+    const ull m = __ballot(pred);
+    if (pred && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(counter, (ull)__popcll(m));
+}
+__global__ void k_adj_edge_keys(const int32_t* tri, i64 nq, i64 nv, u64* keys, int* flags, ull* degenerate) {
+    const i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const i64 t = q / 3;
+    const int j = (int)(q - 3 * t);
+    const int c0 = tri[3 * t], c1 = tri[3 * t + 1], c2 = tri[3 * t + 2];
+    u64 key = (u64)nv << 32;
+    bool degen = false;
+    if (c0 < 0 || c1 < 0 || c2 < 0 || c0 >= nv || c1 >= nv || c2 >= nv) {
+        if (j == 0) atomicOr(&flags[4], 1);
+    } else if (c0 == c1 || c1 == c2 || c0 == c2) {
+        degen = j == 0;
+    } else {
+        const int u = j == 0 ? c0 : j == 1 ? c1 : c2, v = j == 0 ? c1 : j == 1 ? c2 : c0;
+        const int lo = u < v ? u : v, hi = u < v ? v : u;
+        key = ((u64)(u32)lo << 32) | ((u64)(u32)hi << 1) | (u64)(u < v ? 1 : 0);
+    }
+    keys[q] = key;
+    if (degenerate) wave_count(degenerate, degen);
+}
+// head[i] = 1 where an edge's run starts (i <= nq, head[nq] = 0); *nvalid = the number of sides that belong to edges
+__global__ void k_adj_edge_heads(const u64* keys, i64 nq, i64 nv, i64* head, i64* nvalid) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > nq) return;
+    const bool prev_edge = i > 0 && (i64)(keys[i - 1] >> 32) < nv;
+    if (i == nq) {
+        head[i] = 0;
+        if (nq == 0 || prev_edge) *nvalid = nq;
+        return;
+    }
+    const u64 k = keys[i];
+    if ((i64)(k >> 32) >= nv) {
+        head[i] = 0;
+        if (i == 0 || prev_edge) *nvalid = i;
+        return;
+    }
+    head[i] = (i == 0 || (keys[i - 1] >> 1) != (k >> 1)) ? 1 : 0;
+}
+__global__ void k_adj_edge_starts(const i64* eoff, i64 nq, const i64* nvalid, i64* estart) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > nq) return;
+    if (i == nq)
+        estart[eoff[nq]] = *nvalid;
+    else if (eoff[i + 1] > eoff[i])
+        estart[eoff[i]] = i;
+}
+// the table from the run bounds; cap >= the number of edges (the launch's size), any output may be null
+__global__ void k_adj_edge_out(const u64* keys, const i64* estart, const i64* ecount, i64 cap, int32_t* edges, int32_t* uses,
+                               int32_t* forward) {
+    const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= cap || e >= *ecount) return;
+    const i64 b = estart[e], end = estart[e + 1];
+    if (edges) {
+        const u64 k = keys[b];
+        edges[2 * e] = (int32_t)(k >> 32);
+        edges[2 * e + 1] = (int32_t)((k >> 1) & 0x7fffffffu);
+    }
+    if (uses) uses[e] = (int32_t)(end - b);
+    if (forward) {  // the first forward use of the run
+        i64 lo = b, hi = end;
+        while (lo < hi) {
+            const i64 mid = (lo + hi) >> 1;
+            if (keys[mid] & 1)
+                hi = mid;
+            else
+                lo = mid + 1;
+        }
+        forward[e] = (int32_t)(end - lo);
+    }
+}
+__global__ void k_adj_topo_edges(const int32_t* uses, const int32_t* forward, const i64* ecount, i64 cap, ull* cnt) {
+    const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e == 0) cnt[TOPO_EDGES] = (ull)*ecount;
+    if (e >= cap || e >= *ecount) return;
+    const int u = uses[e];
+    wave_count(&cnt[TOPO_BOUNDARY], u == 1);
+    wave_count(&cnt[TOPO_NONMANIFOLD], u >= 3);
+    wave_count(&cnt[TOPO_INCONSISTENT], u == 2 && forward[e] != 1);
+}
+// k_uf_link for an edge list: boundary_only = 1 links the edges with one use only; mark[v] = 1 for every linked vertex
+__global__ void k_uf_link_edges(const int32_t* edges, const int32_t* uses, const i64* ecount, i64 cap, int boundary_only,
+                                int* parent, uint8_t* mark) {
+    const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= cap || e >= *ecount) return;
+    if (boundary_only && uses[e] != 1) return;
+    const int a = edges[2 * e], b = edges[2 * e + 1];
+    mark[a] = 1;
+    mark[b] = 1;
+    uf_union(parent, a, b);
+}
+__global__ void k_adj_topo_vertices(int* parent_all, const uint8_t* used, int* parent_bnd, const uint8_t* on_bnd, i64 nv,
+                                    ull* cnt) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    const bool u = used[i] != 0, b = on_bnd[i] != 0;
+    wave_count(&cnt[TOPO_USED], u);
+    wave_count(&cnt[TOPO_COMPONENTS], u && uf_find(parent_all, (int)i) == (int)i);
+    wave_count(&cnt[TOPO_LOOPS], b && uf_find(parent_bnd, (int)i) == (int)i);
+}
+// both directions of every edge as (source << 32) | (target << 1) | feature; feature vertices are marked
+__global__ void k_adj_csr_pairs(const int32_t* edges, const int32_t* uses, i64 ne, u64* pairs, uint8_t* vfeat) {
+    const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ne) return;
+    const u32 a = (u32)edges[2 * e], b = (u32)edges[2 * e + 1];
+    const u64 feat = uses[e] != 2 ? 1 : 0;
+    pairs[2 * e] = ((u64)a << 32) | ((u64)b << 1) | feat;
+    pairs[2 * e + 1] = ((u64)b << 32) | ((u64)a << 1) | feat;
+    if (feat) {
+        vfeat[a] = 1;
+        vfeat[b] = 1;
+    }
+}
+__global__ void k_smooth_long_flags(const i64* rs, i64 nv, i64* flag) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > nv) return;
+    flag[i] = (i < nv && rs[i + 1] - rs[i] > SMOOTH_CUT) ? 1 : 0;
+}
+__global__ void k_smooth_long_list(const i64* loff, i64 nv, int32_t* list) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nv && loff[i + 1] > loff[i]) list[loff[i]] = (int32_t)i;
+}
+// positions: three doubles per vertex (24-byte slots; slots padded to 32 bytes and read as two aligned 16-byte loads were
+// measured slower)
+__device__ inline void pos_load(const double* p, i64 i, double& x, double& y, double& z) {
+    x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
+}
+__device__ inline void pos_store(double* p, i64 i, double x, double y, double z) {
+    p[3 * i] = x, p[3 * i + 1] = y, p[3 * i + 2] = z;
+}
+__global__ void k_smooth_load(const float* vtx, i64 nv, double* pos, int* flags) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    const float x = vtx[3 * i], y = vtx[3 * i + 1], z = vtx[3 * i + 2];
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) atomicOr(&flags[7], 1);
+    pos_store(pos, i, (double)x, (double)y, (double)z);
+}
+__global__ void k_smooth_store(const double* pos, i64 nv, float* vtx) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    double x, y, z;
+    pos_load(pos, i, x, y, z);
+    vtx[3 * i] = (float)x, vtx[3 * i + 1] = (float)y, vtx[3 * i + 2] = (float)z;
+}
+// which entries of vertex i's row count: none (-1, the vertex stays), the feature entries only (1), all (0)
+__device__ inline int smooth_row_filter(int mode, const uint8_t* vfeat, i64 i) {
+    if (mode == 0 || !vfeat[i]) return 0;
+    return mode == 1 ? -1 : 1;
+}
+__device__ inline void smooth_update(double& px, double& py, double& pz, double sx, double sy, double sz, i64 n, double f) {
+    if (n == 0) return;
+    const double d = (double)n;
+    px = px + f * (sx / d - px);
+    py = py + f * (sy / d - py);
+    pz = pz + f * (sz / d - pz);
+}
+// one step, one thread per row of at most SMOOTH_CUT entries: a sequential sum in ascending neighbour order
+__global__ __launch_bounds__(BLK) void k_smooth_step(const double* __restrict__ pin, double* __restrict__ pout, i64 nv,
+                                                     const i64* __restrict__ rs, const int32_t* __restrict__ adj,
+                                                     const uint8_t* __restrict__ vfeat, int mode, double f) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    const i64 b = rs[i], e = rs[i + 1];
+    if (e - b > SMOOTH_CUT) return;  // k_smooth_step_long writes this row
+    double px, py, pz;
+    pos_load(pin, i, px, py, pz);
+    const int filter = smooth_row_filter(mode, vfeat, i);
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    i64 n = 0;
+    if (filter >= 0)
+        for (i64 k = b; k < e; ++k) {
+            const u32 a = (u32)adj[k];
+            if (filter && !(a & 1)) continue;
+            double x, y, z;
+            pos_load(pin, (i64)(a >> 1), x, y, z);
+            sx += x, sy += y, sz += z;
+            ++n;
+        }
+    smooth_update(px, py, pz, sx, sy, sz, n, f);
+    pos_store(pout, i, px, py, pz);
+}
+// the rows longer than SMOOTH_CUT, one wave per row: lane l sums the entries l, l + 64, ... in order, then the 64 partial
+// sums are added pairwise (xor 32, 16, ... 1): a fixed shape
+__global__ __launch_bounds__(BLK) void k_smooth_step_long(const double* __restrict__ pin, double* __restrict__ pout,
+                                                          const int32_t* __restrict__ rows, i64 nrows,
+                                                          const i64* __restrict__ rs, const int32_t* __restrict__ adj,
+                                                          const uint8_t* __restrict__ vfeat, int mode, double f) {
+    const i64 w = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (w >= nrows) return;  // whole waves leave together
+    const i64 i = rows[w];
+    const i64 b = rs[i], e = rs[i + 1];
+    const int filter = smooth_row_filter(mode, vfeat, i);
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    int n = 0;
+    if (filter >= 0)
+        for (i64 k = b + lane; k < e; k += 64) {
+            const u32 a = (u32)adj[k];
+            if (filter && !(a & 1)) continue;
+            double x, y, z;
+            pos_load(pin, (i64)(a >> 1), x, y, z);
+            sx += x, sy += y, sz += z;
+            ++n;
+        }
+    for (int m = 32; m >= 1; m >>= 1) {
+        sx += __shfl_xor(sx, m);
+        sy += __shfl_xor(sy, m);
+        sz += __shfl_xor(sz, m);
+        n += __shfl_xor(n, m);
+    }
+    if (lane != 0) return;
+    double px, py, pz;
+    pos_load(pin, i, px, py, pz);
+    smooth_update(px, py, pz, sx, sy, sz, (i64)n, f);
+    pos_store(pout, i, px, py, pz);
+}
+
 MeshState& mstate(asr_hip_context* ctx) {
     if (!ctx->mesh_state) ctx->mesh_state = new MeshState();
     return *(MeshState*)ctx->mesh_state;
@@ -1085,6 +1324,218 @@ int asr_mesh_sample(asr_hip_context* ctx, const float* vertices, i64 nv, const i
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_sample: the mesh's area is %g", total);
     k_mesh_sample<<<grid_for(num_samples, BLK), BLK, 0, s>>>(vertices, triangles, nt, prefix, num_samples, seed, points,
                                                               normals, tri);
+    ASR_CHECK_LAUNCH(ctx);
+    return ASR_HIP_OK;
+}
+
+namespace {
+struct EdgeTable {
+    i64 nq = 0;             // sides, an upper bound of the edges
+    u64* keys = nullptr;    // sorted side keys [nq]
+    i64* start = nullptr;   // [edges + 1] first side of every edge
+    i64* count = nullptr;   // the number of edges, on the device
+};
+// sorts the sides of the triangles and finds the runs; nothing is read back (flags[4]: a corner out of range)
+int edge_table(asr_hip_context* ctx, const int32_t* triangles, i64 nt, i64 nv, ull* degenerate, EdgeTable& et) {
+    hipStream_t s = ctx->stream;
+    const i64 nq = 3 * nt;
+    MESH_ALLOC(keys, u64, nq + 1);
+    MESH_ALLOC(keys_s, u64, nq);
+    i64* head = (i64*)keys;  // the unsorted keys are dead once they are sorted
+    MESH_ALLOC(eoff, i64, nq + 1);
+    MESH_ALLOC(estart, i64, nq + 1);
+    MESH_ALLOC(nvalid, i64, 1);
+    if (nq > 0) {
+        k_adj_edge_keys<<<grid_for(nq, BLK), BLK, 0, s>>>(triangles, nq, nv, keys, ctx->d_flags, degenerate);
+        ASR_CHECK_LAUNCH(ctx);
+        ASR_TRY(sort_keys(ctx, ctx->scratch, keys, keys_s, nq, 32 + bits_for(nv + 1)));
+    }
+    k_adj_edge_heads<<<grid_for(nq + 1, BLK), BLK, 0, s>>>(keys_s, nq, nv, head, nvalid);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(scan_counts(ctx, ctx->scratch, head, eoff, nq + 1));
+    k_adj_edge_starts<<<grid_for(nq + 1, BLK), BLK, 0, s>>>(eoff, nq, nvalid, estart);
+    ASR_CHECK_LAUNCH(ctx);
+    et.nq = nq;
+    et.keys = keys_s;
+    et.start = estart;
+    et.count = eoff + nq;
+    return ASR_HIP_OK;
+}
+// the edge count and the flag block in one wait
+int read_count_and_flags(asr_hip_context* ctx, const i64* count, i64* host_count, int* host_flags) {
+    ASR_HIP_CHECK(ctx, hipMemcpyAsync(host_count, count, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
+    return read_flags(ctx, host_flags);
+}
+}  // namespace
+
+int asr_mesh_edges_count(asr_hip_context* ctx, const int32_t* triangles, i64 nt, i64 nv, i64* num_edges) {
+    MeshState& st = mstate(ctx);
+    st = MeshState();
+    *num_edges = 0;
+    if (nt == 0) {
+        st.kind = 4;
+        return ASR_HIP_OK;
+    }
+    ASR_TRY(ensure_flags(ctx));
+    ctx->scratch.reset();
+    ASR_TRY(fresh_flags(ctx));
+    EdgeTable et;
+    ASR_TRY(edge_table(ctx, triangles, nt, nv, nullptr, et));
+    i64 ne = 0;
+    int host[16];
+    ASR_TRY(read_count_and_flags(ctx, et.count, &ne, host));
+    if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_edges: triangle index out of range");
+    st.kind = 4;
+    st.num_edges = *num_edges = ne;
+    st.e_keys = et.keys;
+    st.e_start = et.start;
+    st.e_count = et.count;
+    return ASR_HIP_OK;
+}
+
+int asr_mesh_edges_fill(asr_hip_context* ctx, int32_t* edges, int32_t* uses, int32_t* forward) {
+    MeshState& st = mstate(ctx);
+    if (st.kind != 4) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_edges_fill must follow the matching mesh_edges_count call");
+    st.kind = 0;
+    if (st.num_edges > 0 && (edges || uses || forward)) {
+        k_adj_edge_out<<<grid_for(st.num_edges, BLK), BLK, 0, ctx->stream>>>(st.e_keys, st.e_start, st.e_count, st.num_edges,
+                                                                             edges, uses, forward);
+        ASR_CHECK_LAUNCH(ctx);
+    }
+    ASR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return ASR_HIP_OK;
+}
+
+int asr_mesh_topology_report(asr_hip_context* ctx, const int32_t* triangles, i64 nt, i64 nv, asr_mesh_topology* out) {
+    mstate(ctx) = MeshState();
+    memset(out, 0, sizeof(*out));
+    out->num_vertices = nv;
+    if (nt == 0) return ASR_HIP_OK;
+    ASR_TRY(ensure_flags(ctx));
+    ctx->scratch.reset();
+    hipStream_t s = ctx->stream;
+    ASR_TRY(fresh_flags(ctx));
+    MESH_ALLOC(cnt, ull, TOPO_COUNTERS);
+    ASR_HIP_CHECK(ctx, hipMemsetAsync(cnt, 0, TOPO_COUNTERS * sizeof(ull), s));
+    EdgeTable et;
+    ASR_TRY(edge_table(ctx, triangles, nt, nv, &cnt[TOPO_DEGENERATE], et));
+    // the number of edges stays on the device: the kernels below are launched for its upper bound, the sides
+    const i64 cap = et.nq;
+    MESH_ALLOC(edges, int32_t, 2 * cap);
+    MESH_ALLOC(uses, int32_t, cap);
+    MESH_ALLOC(forward, int32_t, cap);
+    k_adj_edge_out<<<grid_for(cap, BLK), BLK, 0, s>>>(et.keys, et.start, et.count, cap, edges, uses, forward);
+    ASR_CHECK_LAUNCH(ctx);
+    k_adj_topo_edges<<<grid_for(cap, BLK), BLK, 0, s>>>(uses, forward, et.count, cap, cnt);
+    ASR_CHECK_LAUNCH(ctx);
+    if (nv > 0) {  // (nv == 0: every corner is out of range, refused below)
+        MESH_ALLOC(parent_all, int, nv);
+        MESH_ALLOC(parent_bnd, int, nv);
+        MESH_ALLOC(marks, uint8_t, 2 * nv);
+        ASR_HIP_CHECK(ctx, hipMemsetAsync(marks, 0, (size_t)(2 * nv), s));
+        k_uf_init<<<grid_for(nv, BLK), BLK, 0, s>>>(parent_all, nv);
+        ASR_CHECK_LAUNCH(ctx);
+        k_uf_init<<<grid_for(nv, BLK), BLK, 0, s>>>(parent_bnd, nv);
+        ASR_CHECK_LAUNCH(ctx);
+        k_uf_link_edges<<<grid_for(cap, BLK), BLK, 0, s>>>(edges, uses, et.count, cap, 0, parent_all, marks);
+        ASR_CHECK_LAUNCH(ctx);
+        k_uf_link_edges<<<grid_for(cap, BLK), BLK, 0, s>>>(edges, uses, et.count, cap, 1, parent_bnd, marks + nv);
+        ASR_CHECK_LAUNCH(ctx);
+        k_adj_topo_vertices<<<grid_for(nv, BLK), BLK, 0, s>>>(parent_all, marks, parent_bnd, marks + nv, nv, cnt);
+        ASR_CHECK_LAUNCH(ctx);
+    }
+    ull h[TOPO_COUNTERS];
+    int host[16];
+    ASR_HIP_CHECK(ctx, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, s));
+    ASR_TRY(read_flags(ctx, host));
+    if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_topology: triangle index out of range");
+    out->degenerate_triangles = (i64)h[TOPO_DEGENERATE];
+    out->triangles = nt - out->degenerate_triangles;
+    out->edges = (i64)h[TOPO_EDGES];
+    out->boundary_edges = (i64)h[TOPO_BOUNDARY];
+    out->nonmanifold_edges = (i64)h[TOPO_NONMANIFOLD];
+    out->inconsistent_edges = (i64)h[TOPO_INCONSISTENT];
+    out->used_vertices = (i64)h[TOPO_USED];
+    out->components = (i64)h[TOPO_COMPONENTS];
+    out->boundary_loops = (i64)h[TOPO_LOOPS];
+    out->euler = out->used_vertices - out->edges + out->triangles;
+    return ASR_HIP_OK;
+}
+
+int asr_mesh_smooth(asr_hip_context* ctx, const float* vertices, i64 nv, const int32_t* triangles, i64 nt, int iterations,
+                    double lambda, double mu, int boundary, float* vertices_out) {
+    mstate(ctx) = MeshState();
+    ASR_TRY(ensure_flags(ctx));
+    ctx->scratch.reset();
+    ASR_TRY(fresh_flags(ctx));
+    if (nv == 0) {
+        if (nt > 0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: triangle index out of range");
+        return ASR_HIP_OK;
+    }
+    hipStream_t s = ctx->stream;
+    EdgeTable et;
+    ASR_TRY(edge_table(ctx, triangles, nt, nv, nullptr, et));
+    i64 ne = 0;
+    int host[16];
+    ASR_TRY(read_count_and_flags(ctx, et.count, &ne, host));
+    if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: triangle index out of range");
+    // vertex -> neighbour rows: both directions of every edge, sorted; an entry is (neighbour << 1) | feature
+    const i64 np = 2 * ne;
+    MESH_ALLOC(rs, i64, nv + 1);
+    MESH_ALLOC(adj, int32_t, np);
+    MESH_ALLOC(vfeat, uint8_t, nv);
+    ASR_HIP_CHECK(ctx, hipMemsetAsync(vfeat, 0, (size_t)nv, s));
+    if (ne > 0) {
+        MESH_ALLOC(edges, int32_t, 2 * ne);
+        MESH_ALLOC(uses, int32_t, ne);
+        MESH_ALLOC(pairs, u64, np);
+        MESH_ALLOC(pairs_s, u64, np);
+        k_adj_edge_out<<<grid_for(ne, BLK), BLK, 0, s>>>(et.keys, et.start, et.count, ne, edges, uses, nullptr);
+        ASR_CHECK_LAUNCH(ctx);
+        k_adj_csr_pairs<<<grid_for(ne, BLK), BLK, 0, s>>>(edges, uses, ne, pairs, vfeat);
+        ASR_CHECK_LAUNCH(ctx);
+        ASR_TRY(sort_keys(ctx, ctx->scratch, pairs, pairs_s, np, 32 + bits_for(nv)));
+        k_adj_splits<<<grid_for(nv + 1, BLK), BLK, 0, s>>>(pairs_s, np, nv, rs);
+        ASR_CHECK_LAUNCH(ctx);
+        k_adj_payload<<<grid_for(np, BLK), BLK, 0, s>>>(pairs_s, np, adj);
+        ASR_CHECK_LAUNCH(ctx);
+    } else {
+        ASR_HIP_CHECK(ctx, hipMemsetAsync(rs, 0, (size_t)(nv + 1) * sizeof(i64), s));
+    }
+    // the rows a whole wave sums: at most np / (SMOOTH_CUT + 1) of them
+    MESH_ALLOC(lflag, i64, nv + 1);
+    MESH_ALLOC(loff, i64, nv + 1);
+    MESH_ALLOC(long_rows, int32_t, np / (SMOOTH_CUT + 1) + 1);
+    k_smooth_long_flags<<<grid_for(nv + 1, BLK), BLK, 0, s>>>(rs, nv, lflag);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(scan_counts(ctx, ctx->scratch, lflag, loff, nv + 1));
+    k_smooth_long_list<<<grid_for(nv, BLK), BLK, 0, s>>>(loff, nv, long_rows);
+    ASR_CHECK_LAUNCH(ctx);
+    double* pos[2];
+    for (double*& p : pos) {
+        p = arena_alloc<double>(ctx->scratch, (size_t)nv * 3);
+        if (!p) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    }
+    ASR_TRY(fresh_flags(ctx));
+    k_smooth_load<<<grid_for(nv, BLK), BLK, 0, s>>>(vertices, nv, pos[0], ctx->d_flags);
+    ASR_CHECK_LAUNCH(ctx);
+    i64 nlong = 0;
+    ASR_TRY(read_count_and_flags(ctx, loff + nv, &nlong, host));
+    if (host[7]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: a vertex is not finite");
+    int cur = 0;
+    for (int it = 0; it < iterations; ++it)
+        for (int half = 0; half < (mu != 0.0 ? 2 : 1); ++half) {
+            const double f = half ? mu : lambda;
+            k_smooth_step<<<grid_for(nv, BLK), BLK, 0, s>>>(pos[cur], pos[cur ^ 1], nv, rs, adj, vfeat, boundary, f);
+            ASR_CHECK_LAUNCH(ctx);
+            if (nlong > 0) {
+                k_smooth_step_long<<<grid_for(nlong * 64, BLK), BLK, 0, s>>>(pos[cur], pos[cur ^ 1], long_rows, nlong, rs,
+                                                                         adj, vfeat, boundary, f);
+                ASR_CHECK_LAUNCH(ctx);
+            }
+            cur ^= 1;
+        }
+    k_smooth_store<<<grid_for(nv, BLK), BLK, 0, s>>>(pos[cur], nv, vertices_out);
     ASR_CHECK_LAUNCH(ctx);
     return ASR_HIP_OK;
 }

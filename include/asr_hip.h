@@ -517,6 +517,64 @@ int asr_hip_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* fr
                                 int64_t* num_triangles_out);
 int asr_hip_mesh_simplify_fill(asr_hip_context* ctx, float* vertices_out_dev, int32_t* triangles_out_dev,
                                int32_t* vertex_map_out_dev);
+/* ---- mesh adjacency: edge table, topology report, Taubin smoothing (not in the reference).
+ * The contract, which tests/mesh_adjacency_ref.py restates in numpy.  Shared by the three entry points:
+ *   A triangle with two equal corner indices is DEGENERATE: it contributes no edges and is counted.  A corner outside
+ *     [0, num_vertices) is ASR_HIP_EINVAL ("out of range").  Sizes < 2^31 vertices and < 2^31 / 3 triangles.
+ *   Each of the sides (c0,c1), (c1,c2), (c2,c0) of a non-degenerate triangle is one USE of the undirected edge
+ *     (lo, hi) = (min, max) of its ends; the use is FORWARD when it runs lo -> hi.
+ *   EDGES are the distinct (lo, hi) pairs in ascending (lo, hi) order; per edge `uses` is the number of its uses and
+ *     `forward` the number of forward ones.  An edge is BOUNDARY when uses == 1, NON-MANIFOLD when uses >= 3,
+ *     INCONSISTENT when uses == 2 and forward != 1 (its two triangles disagree about the orientation), and a FEATURE
+ *     edge when uses != 2.  A FEATURE VERTEX is an end of a feature edge.
+ *
+ * The edge table.  Count / fill pair like asr_hip_mesh_simplify_*: _count reads the number of edges and the error flag
+ * back once; scratch comes from the context arena and stays valid until _fill, which must be the next mesh call on the
+ * context.  edges_out_dev [E,2] = (lo, hi), uses_out_dev [E], forward_out_dev [E]; any of them may be NULL.
+ * num_triangles == 0 gives E == 0.  Integers only: the same inputs give the same bits. */
+int asr_hip_mesh_edges_count(asr_hip_context* ctx, const int32_t* triangles_dev, int64_t num_triangles,
+                             int64_t num_vertices, int64_t* num_edges_out);
+int asr_hip_mesh_edges_fill(asr_hip_context* ctx, int32_t* edges_out_dev, int32_t* uses_out_dev,
+                            int32_t* forward_out_dev);
+/* The topology report: every count comes from a device reduction, all are read back once.
+ *   used_vertices       vertices referenced by a non-degenerate triangle
+ *   triangles           non-degenerate triangles;  degenerate_triangles: the others
+ *   edges, boundary_edges, nonmanifold_edges, inconsistent_edges: as defined above
+ *   components          connected components of the used vertices under the edges
+ *   boundary_loops      connected components of the graph formed by the boundary edges alone.  This is the number of
+ *                       rims (holes and outer borders) when no vertex has more than two boundary edges; rims that touch
+ *                       in a vertex count as one.
+ *   euler               used_vertices - edges + triangles
+ * A mesh is watertight when it has triangles and no boundary, non-manifold or inconsistent edge; its genus is then
+ * (2 components - euler) / 2.  NOT detected: non-manifold VERTICES (several triangle fans that meet in one vertex
+ * without sharing an edge); such a mesh can pass as edge manifold here. */
+typedef struct asr_mesh_topology {
+    int64_t num_vertices, used_vertices, triangles, degenerate_triangles, edges, boundary_edges, nonmanifold_edges,
+        inconsistent_edges, components, boundary_loops, euler;
+} asr_mesh_topology;
+int asr_hip_mesh_topology(asr_hip_context* ctx, const int32_t* triangles_dev, int64_t num_triangles,
+                          int64_t num_vertices, asr_mesh_topology* out);
+/* Laplacian / Taubin smoothing.  N(i) is the set of distinct vertices that share an edge with vertex i, restricted by
+ * `boundary`:
+ *   0 free    every vertex uses all of its edge neighbours
+ *   1 pinned  feature vertices do not move; the others use all neighbours
+ *   2 along   a feature vertex uses only the far ends of its own feature edges (open rims and non-manifold seams are
+ *             smoothed as curves and do not shrink into the surface); the others use all neighbours
+ * A vertex with an empty N(i) does not move.  One step with factor f is, for all vertices at once and reading only
+ * the previous positions,  p'_i = p_i + f (mean_{j in N(i)} p_j - p_i);  one iteration is a `lambda` step followed by
+ * a `mu` step, mu == 0 means plain Laplacian smoothing (no second step).  Taubin's filter does not shrink the surface
+ * when mu < -lambda (a little more negative than -lambda); the defaults everywhere are lambda = 0.5, mu = -0.53.
+ * Positions are f64 between the steps; the neighbour sum (ascending neighbour index for rows of up to 128 entries; longer
+ * rows as 64 interleaved partial sums added pairwise), the mean and the update are f64 without contraction, the output
+ * is rounded to f32 once at the end.  A vertex that never moves gets its input bits; iterations == 0 copies the input.
+ * No float atomics, every row is summed in a fixed order and shape: the same inputs give the same bits on every run.
+ * vertices_out_dev [num_vertices,3] may equal vertices_dev.
+ * ASR_HIP_EINVAL: iterations outside 0..1000, lambda not in (0, 1], mu not finite or > 0, boundary outside 0..2, a
+ * vertex that is not finite (one check pass before any step, its flag read back once), a corner out of range.
+ * Reads back the number of edges and, with the flags, the number of rows longer than 128 entries. */
+int asr_hip_mesh_smooth(asr_hip_context* ctx, const float* vertices_dev, int64_t num_vertices,
+                        const int32_t* triangles_dev, int64_t num_triangles, int iterations, double lambda, double mu,
+                        int boundary, float* vertices_out_dev);
 /* (asr_hip_implicit_query, the whole-path query on the last forward, is declared after asr_hip_implicit_stage_ms) */
 
 /* ---- whole path: the section of asr::ReconstructSurface between the pre-filter and the
