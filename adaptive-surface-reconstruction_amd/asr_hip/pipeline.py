@@ -225,10 +225,11 @@ class ImplicitPipeline:
             return ops.point_attributes_at(frame, points, radii, attributes, positions, sizes, **kw)
 
     def get(self, name):
-        """copy of one named array of the last forward (see include/asr_hip.h)"""
+        """copy of one named array of the last forward (see include/asr_hip.h), enqueued on torch's current stream"""
         base = name if name in _ARRAY_TYPES else name.rstrip("0123456789")
         if base not in _ARRAY_TYPES:
             raise KeyError(name)
+        self._stream()  # `out` below belongs to torch's current stream: the copy must run there too
         dtype, cols = _ARRAY_TYPES[base]
         nbytes = ctypes.c_size_t(0)
         self.ctx.call("asr_hip_implicit_get", name.encode(), ctypes.c_void_p(0), ctypes.byref(nbytes))

@@ -205,11 +205,23 @@ void asr_hip_context_destroy(asr_hip_context* ctx) {
         if (ctx->aux_t1) (void)hipEventDestroy(ctx->aux_t1);
         delete ctx->aux;
     }
+    if (ctx->switch_ev) (void)hipEventDestroy(ctx->switch_ev);
     release_members(ctx);
     delete ctx;
 }
+// The scratch arena, the flag pool and d_absmax are shared by every stream the context visits, and several entry points
+// return while their kernels still read them: a change of stream orders the new stream behind everything enqueued on the
+// old one.  (The auxiliary search stream needs nothing of its own: it is joined before its entry point returns, and it
+// starts behind an event recorded on ctx->stream, which is behind this one.)  An unchanged stream costs nothing.
 void asr_hip_context_set_stream(asr_hip_context* ctx, void* stream) {
-    if (ctx) ctx->stream = (hipStream_t)stream;
+    if (!ctx || ctx->stream == (hipStream_t)stream) return;
+    const hipStream_t old = ctx->stream;
+    ctx->stream = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess && !ctx->switch_ev) e = hipEventCreateWithFlags(&ctx->switch_ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(ctx->switch_ev, old);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->switch_ev, 0);
+    if (e != hipSuccess) ctx->err = std::string("set_stream: ordering the new stream behind the old one failed: ") + hipGetErrorString(e);
 }
 const char* asr_hip_last_error(const asr_hip_context* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 size_t asr_hip_context_reserved_bytes(const asr_hip_context* ctx) {

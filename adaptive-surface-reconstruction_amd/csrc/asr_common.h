@@ -176,6 +176,7 @@ struct AsrPointIndex {
 
 struct asr_hip_context {
     hipStream_t stream = nullptr;
+    hipEvent_t switch_ev = nullptr;  // asr_hip_context_set_stream: recorded on the old stream, awaited by the new one
     std::string err;
     AsrOptions opt;
     std::map<const void*, asr_conv_plan> conv_plans;  // row splits pointer -> plan of that list (implicit_build)

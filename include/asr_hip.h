@@ -54,6 +54,10 @@ typedef struct asr_octree_frame {
  * reused across calls. */
 int asr_hip_context_create(asr_hip_context** ctx, void* stream);
 void asr_hip_context_destroy(asr_hip_context* ctx);
+/* Moves the context to another stream of its device.  The context's arenas and counters are shared by all streams it
+ * visits, so the move orders the new stream behind everything the context enqueued on the previous one (one event: recorded
+ * there, awaited here); the previous stream must therefore still exist when the stream is changed.  Setting the stream
+ * the context already has does nothing.  A failing HIP call leaves its text in asr_hip_last_error(). */
 void asr_hip_context_set_stream(asr_hip_context* ctx, void* stream);
 const char* asr_hip_last_error(const asr_hip_context* ctx);
 const char* asr_hip_version(void); /* asr::GetVersionStr, cpp/lib/asr.hpp:29 */
