@@ -55,6 +55,19 @@ def _same_device(*tensors):
     return dev
 
 
+def _rows(t, aligned=True):
+    """a float32 matrix as the kernels read it: rows of unit-stride floats, any row stride.  A column slice of a wider
+    buffer is read in place (zero-copy concat) when the MFMA kernel can take it as it is -- aligned: it starts on a
+    16-byte boundary and its row stride is a multiple of 4 floats; everything else is made contiguous, as before"""
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(t)
+    if (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] > 1 and t.stride(1) == 1 and
+            t.stride(0) >= t.shape[1] and
+            (not aligned or (t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0))):
+        return t
+    return _dev(t, torch.float32)
+
+
 i64 = ctypes.c_int64
 
 
@@ -330,25 +343,34 @@ def sparse_conv(filters, inp_features, neighbors_index, neighbors_kernel_index,
                 neighbors_row_splits, inp_importance=None, normalize=False, bias=None, relu=False,
                 residual=None, out=None, return_importance=False, algo=0,
                 neighbors_importance=None, row_perm=None, filters_b=None, bias_b=None, force_nt=0,
-                force_waves=0, num_rows=None):
+                force_waves=0, num_rows=None, out_importance=None):
     """SpecialSparseConv.forward (models/common_torch.py:95-148) in one launch.  filters_b / bias_b:
     optional second filter bank (conv1a + conv1b of a SparseConvBlock in one pass): output columns
     [cout, cout + cout_b); importance, normalize and the returned importance sum then belong to bank b.
     num_rows (with row_perm): compute only the rows row_perm[:num_rows] -- a rank of a sharded run computes the
-    rows it owns and leaves the other rows of `out` untouched."""
+    rows it owns and leaves the other rows of `out` untouched.
+    out_importance: a float32 [num_out] tensor that receives the importance sums (implies return_importance).
+    inp_features and residual may be column slices of wider buffers: such a view is read in place, not copied (see
+    _rows); `out` is always written in place.  With algo 0 or 2 no row of the list may name a slot twice
+    (slots_unique_per_row); algo = 1 takes any list."""
     filters = _dev(filters, torch.float32)
     K, cin, cout = filters.shape
-    inp_features = _dev(inp_features, torch.float32)
+    inp_features = _rows(inp_features)
     nidx = _dev(neighbors_index, torch.int32)
     nk = _dev(neighbors_kernel_index, torch.uint8)
     rs = _dev(neighbors_row_splits, torch.int64)
     v = rs.shape[0] - 1
     if inp_features.shape[1] != cin:
         raise RuntimeError("sparse_conv: feature width does not match the filter")
+    if nidx.numel() == 0:
+        # a list without pairs: an empty tensor has no address and the entry point refuses a null list, although no
+        # kernel would read one -- hand it one-element placeholders
+        nidx = torch.zeros(1, dtype=torch.int32, device=filters.device)
+        nk = torch.zeros(1, dtype=torch.uint8, device=filters.device)
     imp = _dev(inp_importance, torch.float32) if inp_importance is not None else None
     nimp = _dev(neighbors_importance, torch.float32) if neighbors_importance is not None else None
     b = _dev(bias, torch.float32) if bias is not None else None
-    res = _dev(residual, torch.float32) if residual is not None else None
+    res = _rows(residual, aligned=False) if residual is not None else None  # read element by element
     fb = _dev(filters_b, torch.float32) if filters_b is not None else None
     bb = _dev(bias_b, torch.float32) if bias_b is not None else None
     if fb is not None and (fb.dim() != 3 or fb.shape[0] != K or fb.shape[1] != cin):
@@ -357,6 +379,11 @@ def sparse_conv(filters, inp_features, neighbors_index, neighbors_kernel_index,
         out = torch.empty((v, cout + (fb.shape[2] if fb is not None else 0)), dtype=torch.float32,
                           device=filters.device)
     oimp = torch.empty(v, dtype=torch.float32, device=filters.device) if return_importance else None
+    if out_importance is not None:
+        if (out_importance.dtype != torch.float32 or out_importance.shape != (v,) or not out_importance.is_cuda or
+                not out_importance.is_contiguous()):
+            raise RuntimeError("sparse_conv: out_importance must be a contiguous float32 GPU tensor with one element per row")
+        oimp, return_importance = out_importance, True
     a = _lib.SparseConvArgs()
     a.filters = filters.data_ptr()
     a.inp_features = inp_features.data_ptr()
@@ -392,11 +419,27 @@ def sparse_conv(filters, inp_features, neighbors_index, neighbors_kernel_index,
     a.cout_b = fb.shape[2] if fb is not None else 0
     a.force_nt = int(force_nt)
     a.force_waves = int(force_waves)
-    dev = _same_device(filters, inp_features, nidx, nk, rs, imp, nimp, b, res, fb, bb, out, perm)
+    dev = _same_device(filters, inp_features, nidx, nk, rs, imp, nimp, b, res, fb, bb, out, perm, oimp)
     context(dev).call("asr_hip_sparse_conv_f32", ctypes.byref(a))
     if return_importance:
         return out, oimp
     return out
+
+
+def slots_unique_per_row(kernel_index, row_splits):
+    """True when no row of the list names a kernel slot twice: the precondition of sparse_conv with algo 0 or 2 and of
+    the 16-bit kernels.  One sort over the pairs on the tensors' device and one read-back; the tensors of a list may
+    change between calls, so the verdict belongs to this call only (nothing is cached).  Slots are compared as the
+    uint8 values the kernels read."""
+    k = kernel_index.reshape(-1).to(torch.uint8)
+    pairs = k.shape[0]
+    if pairs < 2:
+        return True
+    rs = row_splits.reshape(-1).to(torch.int64)
+    rows = torch.arange(rs.shape[0] - 1, dtype=torch.int64, device=rs.device)
+    row = torch.repeat_interleave(rows, rs[1:] - rs[:-1], output_size=pairs).to(k.device)
+    key = torch.sort(row * 256 + k.to(torch.int64)).values
+    return not bool((key[1:] == key[:-1]).any())
 
 
 def pack_filters(filters, mode, filters_b=None):

@@ -1007,12 +1007,14 @@ __global__ void k_sconv_scalar(asr_sparse_conv_args a) {
     if (a.row_perm) q = a.row_perm[q];  // row list (global row indices)
     float acc = 0.f, norm = 0.f;
     for (i64 p = a.neighbors_row_splits[q]; p < a.neighbors_row_splits[q + 1]; ++p) {
+        const int k = a.neighbors_kernel_index[p];
+        if (k >= a.kernel_size) continue;  // malformed input: slot outside the filter (as k_sconv_mfma)
         int32_t i = a.neighbors_index[p];
         float w = a.neighbors_importance ? a.neighbors_importance[p]
                                          : (a.inp_importance ? a.inp_importance[i] : 1.f);
         norm += w;
         const float* f = a.inp_features + (i64)i * a.inp_ld;
-        const float* W = a.filters + ((i64)a.neighbors_kernel_index[p] * a.cin) * a.cout + oc;
+        const float* W = a.filters + ((i64)k * a.cin) * a.cout + oc;
         for (int ic = 0; ic < a.cin; ++ic) acc += W[(i64)ic * a.cout] * (w * f[ic]);
     }
     if (a.normalize && norm != 0.f) acc /= norm;

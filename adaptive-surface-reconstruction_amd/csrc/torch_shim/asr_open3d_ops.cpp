@@ -63,6 +63,19 @@ at::Tensor dev_as(const at::Tensor& t, at::ScalarType dt, const at::Device& dev)
     return t.to(dev, dt).contiguous();
 }
 
+// Open3D sums the neighbours of a row that share a kernel slot; the MFMA kernel keeps one neighbour per (row, slot)
+// (include/asr_hip.h, asr_hip_sparse_conv_f32).  True when no row names a slot twice: one device-side sort over the
+// pairs and one read-back per call, nothing cached; slots compared as the uint8 values the kernels read (the same
+// predicate as asr_hip.ops.slots_unique_per_row, which has the unit test).
+bool slots_unique_per_row(const at::Tensor& kidx, const at::Tensor& rs) {
+    const int64_t pairs = kidx.numel();
+    if (pairs < 2) return true;
+    const at::Tensor lens = rs.slice(0, 1) - rs.slice(0, 0, -1);
+    const at::Tensor row = at::repeat_interleave(at::arange(rs.size(0) - 1, rs.options()), lens, 0, pairs);
+    const at::Tensor key = std::get<0>(at::sort(row * 256 + kidx.to(at::kLong), 0));
+    return !key.slice(0, 1).eq(key.slice(0, 0, -1)).any().item<bool>();
+}
+
 at::Tensor sparse_conv(const at::Tensor& filters, const at::Tensor& inp_features, const at::Tensor& inp_importance,
                        const at::Tensor& neighbors_index, const at::Tensor& neighbors_kernel_index,
                        const at::Tensor& neighbors_importance, const at::Tensor& neighbors_row_splits, bool normalize,
@@ -71,11 +84,16 @@ at::Tensor sparse_conv(const at::Tensor& filters, const at::Tensor& inp_features
     TORCH_CHECK(filters.dim() == 3, "sparse_conv: filters must be [K, cin, cout]");
     const auto dev = filters.device();
     const at::Tensor w = dev_as(filters, at::kFloat, dev), f = dev_as(inp_features, at::kFloat, dev);
-    const at::Tensor idx = dev_as(neighbors_index, at::kInt, dev), kidx = dev_as(neighbors_kernel_index, at::kByte, dev);
+    at::Tensor idx = dev_as(neighbors_index, at::kInt, dev), kidx = dev_as(neighbors_kernel_index, at::kByte, dev);
     const at::Tensor rs = dev_as(neighbors_row_splits, at::kLong, dev);
     at::Tensor nimp;
     if (neighbors_importance.numel()) nimp = dev_as(neighbors_importance, at::kFloat, dev);
     TORCH_CHECK(f.dim() == 2 && f.size(1) == w.size(1), "sparse_conv: feature width does not match the filter");
+    const bool unique = slots_unique_per_row(kidx, rs);
+    if (idx.numel() == 0) {  // no pairs: an empty tensor has no address, the entry point refuses a null list
+        idx = at::zeros({1}, idx.options());
+        kidx = at::zeros({1}, kidx.options());
+    }
     const int64_t v = rs.size(0) - 1;
     at::Tensor out = at::empty({v, w.size(2)}, f.options());
     asr_sparse_conv_args a = {};  // zero: optional fields inactive
@@ -94,6 +112,7 @@ at::Tensor sparse_conv(const at::Tensor& filters, const at::Tensor& inp_features
     a.normalize = normalize ? 1 : 0;
     a.out = out.data_ptr<float>();
     a.out_ld = out.stride(0);
+    a.algo = unique ? 0 : 1;  // a row that repeats a slot: the scalar kernel, which takes any list
     Locked held = context_for(w);  // released when the op returns
     asr_hip_context* c = held.c;
     check(c, asr_hip_sparse_conv_f32(c, &a), "sparse_conv");

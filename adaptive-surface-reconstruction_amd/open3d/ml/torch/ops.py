@@ -29,6 +29,13 @@ def _hip():
     return hip_ops
 
 
+def _algo_for(kernel_index, row_splits):
+    """Open3D sums the neighbours of a row that share a kernel slot; the MFMA kernel keeps one neighbour per (row, slot).
+    Every list handed to the library is therefore tested here (one device-side sort, one read-back, no cache): a list
+    with a repeated slot goes to the scalar kernel, which takes any list."""
+    return 0 if _hip().slots_unique_per_row(kernel_index, row_splits) else 1
+
+
 def _sparse_conv_gpu(filters, inp_features, inp_importance, neighbors_index,
                      neighbors_kernel_index, neighbors_importance, neighbors_row_splits,
                      normalize=False, max_temp_mem_MB=64):
@@ -37,7 +44,8 @@ def _sparse_conv_gpu(filters, inp_features, inp_importance, neighbors_index,
     nimp = neighbors_importance.to(filters.device) if neighbors_importance.numel() else None
     return _hip().sparse_conv(filters, inp_features, neighbors_index, neighbors_kernel_index,
                               neighbors_row_splits, normalize=normalize,
-                              neighbors_importance=nimp)
+                              neighbors_importance=nimp,
+                              algo=_algo_for(neighbors_kernel_index, neighbors_row_splits))
 
 
 def _continuous_conv_gpu(filters, out_positions, extents, offset, inp_positions, inp_features,
@@ -108,8 +116,11 @@ def _sparse_conv_backward(ctx, grad):
         order = torch.argsort(idx.long(), stable=True)
         inv_rs = torch.zeros(n_in + 1, dtype=torch.int64, device=f.device)
         inv_rs[1:] = torch.cumsum(torch.bincount(idx.long(), minlength=n_in), 0)
+        # two outputs that read one input through the same slot: that input's row of the transposed list names the slot twice
+        inv_kidx = kidx[order]
         g_feats = _hip().sparse_conv(filters.transpose(1, 2).contiguous(), grad, row[order].to(torch.int32),
-                                     kidx[order], inv_rs, neighbors_importance=nimp[order] if has_imp else None)
+                                     inv_kidx, inv_rs, neighbors_importance=nimp[order] if has_imp else None,
+                                     algo=_algo_for(inv_kidx, inv_rs))
     if ctx.needs_input_grad[0]:
         g_filters = torch.zeros_like(filters)
         src = f.index_select(0, idx.long())

@@ -327,6 +327,11 @@ typedef struct asr_sparse_conv_args {
      * `out`) -- the inp_absmax of the convolutions that read `out`; the caller zeroes it.  NULL: not kept. */
     uint32_t* out_absmax;
 } asr_sparse_conv_args;
+/* The call is asynchronous and does not inspect the list.  With algo 0 or 2 (the MFMA kernel keeps one neighbour per
+ * (row, slot)) a row may name every kernel slot at most once (true for all lists of the reference's grids,
+ * cpp/lib/grid.cpp:99-170, 229-240); a row that names a slot twice gets one of the two neighbours, unspecified which,
+ * and both importances in its sum.  algo = 1 (the scalar kernel) takes any list and sums repeated slots.  Both kernels
+ * skip an entry whose slot is >= kernel_size, its importance included. */
 int asr_hip_sparse_conv_f32(asr_hip_context* ctx, const asr_sparse_conv_args* args);
 /* Launch statistics of the MFMA sparse conv since the last reset: text "NT,KC,IMP,WAVES,DUAL:count;..."
  * (template instance k_sconv_mfma<NT,KC,IMP,WAVES,DUAL> -> number of launches), NUL terminated.  The 16-bit

@@ -11,6 +11,7 @@ import torch
 import parity
 from asr_hip import synth
 from oracle import oracle as O
+from sconv_lists import dense_autograd_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -350,18 +351,10 @@ def test_sparse_conv_backward_against_torch_autograd(geo, gpu):
                                    neighbors_row_splits=_t(rs, gpu), normalize=normalize)
         out.backward(_t(gout, gpu))
         # dense fp64 reference on the CPU
-        fr = torch.from_numpy(f0).double().requires_grad_(True)
-        Wr = torch.from_numpy(W0).double().requires_grad_(True)
-        row = torch.repeat_interleave(torch.arange(v), torch.from_numpy(np.diff(rs)))
-        w = torch.from_numpy(imp).double() if with_imp else torch.ones(len(idx), dtype=torch.float64)
-        contrib = torch.einsum("pc,pco->po", fr[torch.from_numpy(idx).long()] * w[:, None], Wr[torch.from_numpy(kidx).long()])
-        ref = torch.zeros((v, cout), dtype=torch.float64).index_add(0, row, contrib)
-        if normalize:
-            ref = ref / torch.zeros(v, dtype=torch.float64).index_add(0, row, w)[:, None]
-        _close(out.detach().cpu().numpy(), ref.detach().numpy())
-        ref.backward(torch.from_numpy(gout).double())
-        _close(f.grad.cpu().numpy(), fr.grad.numpy(), 2e-5, 2e-5)
-        _close(W.grad.cpu().numpy(), Wr.grad.numpy(), 2e-5, 2e-5)
+        ref, f_grad, W_grad = dense_autograd_reference(f0, W0, idx, kidx, rs, imp if with_imp else None, normalize, gout)
+        _close(out.detach().cpu().numpy(), ref)
+        _close(f.grad.cpu().numpy(), f_grad, 2e-5, 2e-5)
+        _close(W.grad.cpu().numpy(), W_grad, 2e-5, 2e-5)
     vals = _t(rng.uniform(0, 1, size=len(idx)).astype(np.float32), gpu).requires_grad_(True)
     s = ml3d.ops.reduce_subarrays_sum(vals, _t(rs, gpu))
     s.backward(torch.arange(v, dtype=torch.float32, device=gpu))

@@ -43,6 +43,15 @@ def main():
     parity.assert_close(got.cpu().numpy(), O.sparse_conv(W, f, idx, kidx, nimp, rs, True))
     got = torch.ops.open3d.reduce_subarrays_sum(t(nimp), t(rs))
     parity.assert_close(got.cpu().numpy(), O.reduce_subarrays_sum(nimp, rs))
+    # a row that names a slot twice is summed, as Open3D does, and a list without pairs is not an error
+    import sconv_lists as L
+    for lst in (L.duplicates(), L.duplicates55(), L.all_empty()):
+        d = L.make_data(lst, 32, 32)
+        for imp, normalize in ((empty, False), (t(d["pimp"]), True)):
+            got = torch.ops.open3d.sparse_conv(t(d["W"]), t(d["f"]), empty, t(lst.idx), t(lst.slots), imp, t(lst.rs),
+                                               normalize, 64)
+            parity.assert_close(got.cpu().numpy(), L.reference(O, lst, d["W"], d["f"], d["pimp"] if imp.numel() else None,
+                                                               normalize))
     # inversion of the up list (with attributes)
     ui, uk, ur = geo["up_neighbors_index0"], geo["up_neighbors_kernel_index0"], geo["up_neighbors_row_splits0"]
     n_coarse = len(geo["voxel_sizes1"])
