@@ -583,35 +583,76 @@ def row_groups(neighbors_kernel_index, neighbors_row_splits, segment_rows=0):
     nk = _dev(neighbors_kernel_index, torch.uint8)
     rs = _dev(neighbors_row_splits, torch.int64)
     v = rs.shape[0] - 1
+    if nk.numel() == 0:  # a list without pairs: an empty tensor has no address (see sparse_conv); no kernel reads it
+        nk = torch.zeros(1, dtype=torch.uint8, device=rs.device)
     perm = torch.empty(v, dtype=torch.int32, device=rs.device)
     context(_same_device(nk, rs)).call("asr_hip_row_groups", ptr(nk), ptr(rs), i64(v), i64(segment_rows), ptr(perm))
     return perm
 
 
+def _pair_rows(rs, pairs):
+    """the row of every pair of a list with row splits rs (int64 [pairs])"""
+    rows = torch.arange(rs.shape[0] - 1, dtype=torch.int64, device=rs.device)
+    return torch.repeat_interleave(rows, rs[1:] - rs[:-1], output_size=pairs)
+
+
 def invert_neighbors_list(num_points, inp_neighbors_index, inp_neighbors_row_splits,
                           inp_neighbors_attributes=None):
+    """open3d::invert_neighbors_list -> (index int32, row_splits int64 [num_points + 1], attributes).  The attributes
+    come back in their own dtype, bit for bit: uint8 (the kernel indices of the model) travel through the kernel, every
+    other type is permuted with the same stable order by input (one device-side sort); nothing is ever cast."""
     idx = _dev(inp_neighbors_index, torch.int32)
     rs = _dev(inp_neighbors_row_splits, torch.int64)
-    attr = None
+    attr = carried = None
     if inp_neighbors_attributes is not None and inp_neighbors_attributes.numel():
-        attr = _dev(inp_neighbors_attributes, torch.uint8)
+        a = inp_neighbors_attributes
+        if not a.is_cuda:
+            raise AsrHipError("expected a GPU tensor: the HIP path has no CPU fallback")
+        if a.shape[0] != idx.shape[0]:
+            raise AsrHipError("invert_neighbors_list: one attribute per pair expected")
+        if a.dtype == torch.uint8 and a.dim() == 1:
+            attr = a.contiguous()
+        else:
+            carried = a
     p = idx.shape[0]
     out_idx = torch.empty(p, dtype=torch.int32, device=idx.device)
     out_rs = torch.empty(num_points + 1, dtype=torch.int64, device=idx.device)
     out_attr = torch.empty(p if attr is not None else 0, dtype=torch.uint8, device=idx.device)
-    context(_same_device(idx, rs, attr)).call("asr_hip_invert_neighbors_list", i64(num_points), ptr(idx), ptr(rs),
+    context(_same_device(idx, rs, attr, carried)).call("asr_hip_invert_neighbors_list", i64(num_points), ptr(idx), ptr(rs),
                    i64(rs.shape[0] - 1), ptr(attr), ptr(out_idx), ptr(out_rs),
                    ptr(out_attr) if attr is not None else ctypes.c_void_p(0))
+    if carried is not None:
+        out_attr = carried.index_select(0, torch.argsort(idx.long(), stable=True))
     return out_idx, out_rs, out_attr
 
 
+_REDUCE_EXACT_TYPES = (torch.float64, torch.int32, torch.int64)
+
+
 def reduce_subarrays_sum(values, row_splits, gather_index=None):
-    values = _dev(values, torch.float32)
+    """open3d::reduce_subarrays_sum (of values[gather_index] when given) in the dtype of `values`: float32 through the
+    kernel (sequential f32 sum per row); float64, int32 and int64 are summed in their own type on the device
+    (index_add_); every other dtype is refused."""
+    if not isinstance(values, torch.Tensor):
+        values = torch.as_tensor(values)
     rs = _dev(row_splits, torch.int64)
     g = _dev(gather_index, torch.int32) if gather_index is not None else None
-    out = torch.empty(rs.shape[0] - 1, dtype=torch.float32, device=values.device)
+    rows = rs.shape[0] - 1
+    if values.dtype in _REDUCE_EXACT_TYPES:
+        if not values.is_cuda:
+            raise AsrHipError("expected a GPU tensor: the HIP path has no CPU fallback")
+        _same_device(values, rs, g)
+        x = values.reshape(-1) if g is None else values.reshape(-1).index_select(0, g.long())
+        out = torch.zeros(rows, dtype=values.dtype, device=values.device)
+        return out.index_add_(0, _pair_rows(rs, x.shape[0]), x) if x.shape[0] else out
+    if values.dtype != torch.float32:
+        raise AsrHipError("reduce_subarrays_sum: values must be float32, float64, int32 or int64, not %s" % values.dtype)
+    values = _dev(values, torch.float32)
+    if values.numel() == 0:
+        return torch.zeros(rows, dtype=torch.float32, device=rs.device)  # no value at all: every row is empty
+    out = torch.empty(rows, dtype=torch.float32, device=values.device)
     context(_same_device(values, rs, g)).call("asr_hip_reduce_subarrays_sum", ptr(values), ptr(g), ptr(rs),
-                   i64(rs.shape[0] - 1), ptr(out))
+                   i64(rows), ptr(out))
     return out
 
 

@@ -661,6 +661,9 @@ int asr_hip_decode_mlp(asr_hip_context* ctx, const float* code, int64_t v, int c
                        const float* b1, int h1, const float* w2, const float* b2, int h2,
                        const float* w3, const float* sizes, float* out) {
     CTX_GUARD(ctx);
+    // (before the null check: a tensor of width 0 has no address)
+    if (v > 0 && (c < 1 || c > 64 || h1 < 1 || h1 > 64 || h2 < 1 || h2 > 64))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "decode_mlp: layer widths must be 1..64");
     if (v > 0 && (!code || !w1 || !b1 || !w2 || !b2 || !w3 || !out))
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "decode_mlp: null argument");
     return asr_conv_decode(ctx, code, v, c, w1, b1, h1, w2, b2, h2, w3, sizes, out);

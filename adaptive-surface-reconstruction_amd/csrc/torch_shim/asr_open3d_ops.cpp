@@ -154,32 +154,51 @@ at::Tensor continuous_conv(const at::Tensor& filters, const at::Tensor& out_posi
     return out;
 }
 
+// The attributes keep their dtype and their bits: uint8 (the kernel indices of the model) travel through the kernel, every
+// other type is permuted with the same stable order by input (one device-side sort).  Nothing is cast.
 std::tuple<at::Tensor, at::Tensor, at::Tensor> invert_neighbors_list(int64_t num_points, const at::Tensor& inp_index,
                                                                      const at::Tensor& inp_row_splits,
                                                                      const at::Tensor& inp_attributes) {
     const auto dev = inp_index.device();
     const at::Tensor idx = dev_as(inp_index, at::kInt, dev), rs = dev_as(inp_row_splits, at::kLong, dev);
     const bool has_attr = inp_attributes.numel() > 0;
+    TORCH_CHECK(!has_attr || inp_attributes.size(0) == idx.size(0), "invert_neighbors_list: one attribute per pair expected");
+    const bool in_kernel = has_attr && inp_attributes.scalar_type() == at::kByte && inp_attributes.dim() == 1;
     at::Tensor attr;
-    if (has_attr) attr = dev_as(inp_attributes, at::kByte, dev);
+    if (in_kernel) attr = dev_as(inp_attributes, at::kByte, dev);
     at::Tensor out_idx = at::empty({idx.size(0)}, idx.options());
     at::Tensor out_rs = at::empty({num_points + 1}, rs.options());
-    at::Tensor out_attr = has_attr ? at::empty({idx.size(0)}, attr.options()) : at::empty({0}, inp_attributes.options());
-    Locked held = context_for(idx);  // released when the op returns
-    asr_hip_context* c = held.c;
-    check(c,
-          asr_hip_invert_neighbors_list(c, num_points, idx.data_ptr<int32_t>(), rs.data_ptr<int64_t>(), rs.size(0) - 1,
-                                        has_attr ? attr.data_ptr<uint8_t>() : nullptr, out_idx.data_ptr<int32_t>(),
-                                        out_rs.data_ptr<int64_t>(), has_attr ? out_attr.data_ptr<uint8_t>() : nullptr),
-          "invert_neighbors_list");
-    if (has_attr && inp_attributes.scalar_type() != at::kByte) out_attr = out_attr.to(inp_attributes.scalar_type());
+    at::Tensor out_attr = in_kernel ? at::empty({idx.size(0)}, attr.options()) : at::empty({0}, inp_attributes.options().device(dev));
+    {
+        Locked held = context_for(idx);  // released at the end of the block
+        asr_hip_context* c = held.c;
+        check(c,
+              asr_hip_invert_neighbors_list(c, num_points, idx.data_ptr<int32_t>(), rs.data_ptr<int64_t>(), rs.size(0) - 1,
+                                            in_kernel ? attr.data_ptr<uint8_t>() : nullptr, out_idx.data_ptr<int32_t>(),
+                                            out_rs.data_ptr<int64_t>(), in_kernel ? out_attr.data_ptr<uint8_t>() : nullptr),
+              "invert_neighbors_list");
+    }
+    if (has_attr && !in_kernel)
+        out_attr = inp_attributes.to(dev).index_select(0, at::argsort(idx.to(at::kLong), /*stable=*/true, 0, false));
     return std::make_tuple(out_idx.to(inp_index.scalar_type()), out_rs, out_attr);
 }
 
+// In the dtype of `values`: float32 through the kernel; float64, int32 and int64 summed in their own type on the device;
+// every other dtype is refused (never summed in float32 and cast back).
 at::Tensor reduce_subarrays_sum(const at::Tensor& values, const at::Tensor& row_splits) {
     const auto dev = values.device();
-    const at::Tensor val = dev_as(values, at::kFloat, dev), rs = dev_as(row_splits, at::kLong, dev);
+    const auto dt = values.scalar_type();
+    TORCH_CHECK(dt == at::kFloat || dt == at::kDouble || dt == at::kInt || dt == at::kLong,
+                "reduce_subarrays_sum: values must be float32, float64, int32 or int64");
+    const at::Tensor val = dev_as(values, dt, dev).reshape({-1}), rs = dev_as(row_splits, at::kLong, dev);
     const int64_t rows = rs.size(0) - 1;
+    if (dt != at::kFloat || val.numel() == 0) {  // (no value at all: every row is empty)
+        at::Tensor out = at::zeros({rows}, val.options());
+        if (val.numel() == 0) return out;
+        const at::Tensor lens = rs.slice(0, 1) - rs.slice(0, 0, -1);
+        const at::Tensor row = at::repeat_interleave(at::arange(rows, rs.options()), lens, 0, val.numel());
+        return out.index_add_(0, row, val);
+    }
     at::Tensor out = at::empty({rows}, val.options());
     Locked held = context_for(val);  // released when the op returns
     asr_hip_context* c = held.c;

@@ -66,11 +66,12 @@ def _continuous_conv_gpu(filters, out_positions, extents, offset, inp_positions,
 
 def _invert_gpu(num_points, inp_neighbors_index, inp_neighbors_row_splits,
                 inp_neighbors_attributes):
+    # the attributes keep their dtype and their bits (asr_hip.ops.invert_neighbors_list)
     idx, rs, attr = _hip().invert_neighbors_list(num_points, inp_neighbors_index,
                                                  inp_neighbors_row_splits,
                                                  inp_neighbors_attributes)
-    if inp_neighbors_attributes.numel() and attr.dtype != inp_neighbors_attributes.dtype:
-        attr = attr.to(inp_neighbors_attributes.dtype)
+    if not inp_neighbors_attributes.numel():
+        attr = torch.empty(0, dtype=inp_neighbors_attributes.dtype, device=idx.device)
     return idx.to(inp_neighbors_index.dtype), rs, attr
 
 

@@ -400,7 +400,12 @@ int asr_hip_convert_f16(asr_hip_context* ctx, const void* in_dev, int64_t n, voi
 
 /* MFMA tiling order for asr_hip_sparse_conv_f32: reorders the rows of a CSR inside segments of
  * `segment_rows` consecutive rows (0 = default) by their set of kernel slots, so that 16-row MFMA
- * tiles see few distinct slots. perm_out_dev [num_rows] goes into asr_sparse_conv_args.row_perm. */
+ * tiles see few distinct slots. perm_out_dev [num_rows] goes into asr_sparse_conv_args.row_perm.
+ * The order: rows stably by (row / segment_rows, slot mask, row), the mask being the OR of 1 << slot over the
+ * row (an empty row: 0); then, with option row_lpt and more than 128 rows, the 128-row chunks of that order
+ * stably by (128 c / segment_rows) * 128 + 127 - cost, cost = slots in the union of the chunk's first 64 rows
+ * + the same for its second 64 rows, 0 for the partial last chunk.  Always a permutation; for segment_rows a
+ * multiple of 128 every row stays inside its segment (tests/list_ops_ref.py). */
 int asr_hip_row_groups(asr_hip_context* ctx, const uint8_t* kernel_index_dev,
                        const int64_t* row_splits_dev, int64_t num_rows, int64_t segment_rows,
                        int32_t* perm_out_dev);
@@ -422,7 +427,7 @@ int asr_hip_reduce_subarrays_sum(asr_hip_context* ctx, const float* values_dev,
 /* ---- a14: UNet5.decode with zero shifts + sdf scale
  *      (net_definitions_torch.py:655-666, cpp/lib/asr.cpp:324-336) ------------------------ */
 /* w1 [h1, 3+c], b1 [h1], w2 [h2,h1], b2 [h2], w3 [2,h2] (torch Linear layout);
- * sizes may be NULL (no sdf scale). out [v,2]. */
+ * sizes may be NULL (no sdf scale). out [v,2].  c, h1, h2 in 1..64, else ASR_HIP_EINVAL. */
 int asr_hip_decode_mlp(asr_hip_context* ctx, const float* code_dev, int64_t v, int c,
                        const float* w1_dev, const float* b1_dev, int h1, const float* w2_dev,
                        const float* b2_dev, int h2, const float* w3_dev,

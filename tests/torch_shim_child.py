@@ -59,6 +59,15 @@ def main():
     ri, rr, ra = O.invert_neighbors_list(n_coarse, ui, ur, uk)
     assert np.array_equal(gi.cpu().numpy(), ri) and np.array_equal(gr.cpu().numpy(), rr)
     assert np.array_equal(ga.cpu().numpy(), ra)
+    # attributes of another type come back in that type, bit for bit (not through uint8), and so do float64 sums
+    fa = (np.arange(len(ui)) + 0.37).astype(np.float32)
+    gi, gr, ga = torch.ops.open3d.invert_neighbors_list(n_coarse, t(ui), t(ur), t(fa))
+    assert ga.dtype == torch.float32 and np.array_equal(ga.cpu().numpy(), fa[np.argsort(ui, kind="stable")])
+    assert np.array_equal(gi.cpu().numpy(), ri) and np.array_equal(gr.cpu().numpy(), rr)
+    xd = 1.0 + np.arange(1, len(idx) + 1) * 2.0 ** -30  # every partial sum is exact in float64
+    got = torch.ops.open3d.reduce_subarrays_sum(t(xd), t(rs))
+    assert got.dtype == torch.float64
+    assert np.array_equal(got.cpu().numpy(), np.array([xd[rs[q]:rs[q + 1]].sum() for q in range(v)]))
     # continuous conv of the aggregation block
     centers, sizes = geo["voxel_centers0"], geo["voxel_sizes0"]
     ai, ar = geo["aggregation_neighbors_index"], geo["aggregation_row_splits"]
