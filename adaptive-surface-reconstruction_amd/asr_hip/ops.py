@@ -6,6 +6,7 @@ Names and argument meaning follow the reference interfaces they stand in for:
   continuous_conv / sparse_conv / invert_neighbors_list / reduce_subarrays_sum
                                              -> open3d.ml.torch.ops used by models/common_torch.py
 """
+import contextlib
 import ctypes
 
 import torch
@@ -30,6 +31,27 @@ def context(device=None):
             ctx = _ctx[index] = Context()
     ctx.set_stream(torch.cuda.current_stream(index))
     return ctx
+
+
+@contextlib.contextmanager
+def fresh_context(device=None):
+    """`with fresh_context(device) as ctx`: the operators of this module (and what is built on them, KDTree for one) run
+    on a new context inside the block -- no option set, no table grown, nothing cached by an earlier call.  The block's
+    context is closed at its end and the device's earlier one, untouched meanwhile, serves again."""
+    if device is not None and torch.device(device).index is not None:
+        index = torch.device(device).index
+    else:
+        index = torch.cuda.current_device()
+    old = _ctx.pop(index, None)
+    try:
+        yield context(index)
+    finally:
+        torch.cuda.synchronize(index)
+        new = _ctx.pop(index, None)
+        if new is not None:
+            new.close()
+        if old is not None:
+            _ctx[index] = old
 
 
 def _dev(t, dtype):

@@ -150,6 +150,10 @@ int asr_hip_context_get_option(asr_hip_context* ctx, const char* name, int64_t* 
         *value = ctx->search_overlapped && ctx->aux ? ctx->aux->search_extras : ctx->search_extras;
         return ASR_HIP_OK;
     }
+    if (!strcmp(name, "table_regrows")) {  // read-only diagnostic: tables rebuilt larger, cumulative, both contexts
+        *value = ctx->table_regrows + (ctx->aux ? ctx->aux->table_regrows : 0);
+        return ASR_HIP_OK;
+    }
     for (const OptEntry& o : k_options)
         if (!strcmp(name, o.name)) {
             *value = ctx->opt.*(o.field);

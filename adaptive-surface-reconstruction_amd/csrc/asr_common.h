@@ -214,6 +214,11 @@ struct asr_hip_context {
     AsrPointIndex pindex;                // asr_geom_presort
     i64 shard_prefix_hint = 0;           // rows of the importance prefix the last sharded build needed
     int search_extras = 0;               // pairs the last aligned search took from the rounding margin (diagnostic)
+    const u64* nb_grow_keys = nullptr;   // asr_geom_grid_neighbors_count: the keys of the last call, their number and the
+    i64 nb_grow_v = 0;                   // enlargement (log2) its key map needed -- the next _fill call on these keys starts
+                                         // there and clears the note (nb_grow_keys == nullptr: none)
+    int nb_grow = 0;
+    i64 table_regrows = 0;               // hash tables rebuilt larger after an overflow since the context exists (diagnostic)
     int leaf_lmin = -1, leaf_lmax = -1;  // levels of the first / last leaf of the last octree
     float* values = nullptr;
     float* feats1 = nullptr;

@@ -2329,6 +2329,7 @@ static int grow_keys(asr_hip_context* ctx, Arena& arena, const asr_octree_frame*
     int host[16];
     u64 cap = next_pow2((u64)std::max<i64>(i64(1) << 16, 8 * n));
     for (int attempt = 0; attempt < 6; ++attempt, cap <<= 2) {
+        if (attempt) ++ctx->table_regrows;
         HashTab t;
         ASR_TRY(make_table(ctx, arena, cap, false, t));
         const int lcap = (int)std::min<u64>(cap / 2, u64(1) << 30);
@@ -2393,6 +2394,7 @@ int asr_geom_octree_build(asr_hip_context* ctx, const asr_octree_frame* frame, c
     u64 cap = next_pow2((u64)std::max<i64>(i64(1) << 16, 2 * std::max(std::max(n, 4 * num_grown), num_extra)));
     int host[16];
     for (int attempt = 0; attempt < 7; ++attempt, cap <<= 2) {
+        if (attempt) ++ctx->table_regrows;
         ctx->scratch.reset();
         HashTab t;
         ASR_TRY(make_table(ctx, ctx->scratch, cap, false, t));
@@ -2493,10 +2495,12 @@ int asr_geom_octree_build(asr_hip_context* ctx, const asr_octree_frame* frame, c
 // uses them, enqueued on ctx->stream -- and ONE read-back of the overflow flag.  A map that lost keys (see TabProbe:
 // lattice-like key sets fill "their" positions of the 64-slot buckets early) is rebuilt four times the size and `pass`
 // run again, so that every caller either sees all keys or fails; none drops neighbours silently.
+// grow0 / grow_out: the enlargement to start with and the one that sufficed (the _fill call of a stand-alone operator starts
+// where its _count call ended instead of overflowing its way up again).
 template <class Pass>
-static int nb_key_maps(asr_hip_context* ctx, NbBatch& b, Pass&& pass) {
+static int nb_key_maps(asr_hip_context* ctx, NbBatch& b, Pass&& pass, int grow0 = 0, int* grow_out = nullptr) {
     ASR_TRY(ensure_flags(ctx));
-    for (int grow = 0;; grow += 2) {
+    for (int grow = grow0;; grow += 2) {
         u64 caps[NB_MAX_JOBS], cap_sum = 0;
         for (int j = 0; j < b.n; ++j) {
             caps[j] = next_pow2((u64)std::max<i64>(1024, 2 * b.v[j])) << grow;
@@ -2517,8 +2521,12 @@ static int nb_key_maps(asr_hip_context* ctx, NbBatch& b, Pass&& pass) {
         ASR_TRY(pass());
         int host[16];
         ASR_TRY(read_flags(ctx, host));
-        if (!host[1]) return ASR_HIP_OK;
+        if (!host[1]) {
+            if (grow_out) *grow_out = grow;
+            return ASR_HIP_OK;
+        }
         if (grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "voxel key map overflow");
+        ++ctx->table_regrows;
     }
 }
 
@@ -2556,6 +2564,7 @@ int asr_geom_grid_neighbors_count(asr_hip_context* ctx, const u64* keys, i64 v, 
         ASR_HIP_CHECK(ctx, hipMemsetAsync(rs, 0, sizeof(i64), ctx->stream));
         return ASR_HIP_OK;
     }
+    ctx->nb_grow_keys = nullptr;  // (set again below only when this call succeeds)
     NbBatch b = nb_one_grid(keys, v);
     if (rows) {  // the row list becomes the batch's row filter: 1 at the listed rows
         int32_t* mark = arena_alloc<int32_t>(ctx->scratch, v);
@@ -2570,7 +2579,9 @@ int asr_geom_grid_neighbors_count(asr_hip_context* ctx, const u64* keys, i64 v, 
         k_neighbors_count_batch<<<grid_for(v + 1, BLK), BLK, 0, ctx->stream>>>(b, counts, nullptr, nullptr, nullptr);
         ASR_CHECK_LAUNCH(ctx);
         return scan_counts(ctx, ctx->scratch, counts, rs, v + 1);
-    }));
+    }, 0, &ctx->nb_grow));
+    ctx->nb_grow_keys = keys;
+    ctx->nb_grow_v = v;
     return read_i64(ctx, rs + v, num_pairs);
 }
 // rows: checked only; the rows that are not listed have no entries in rs and are skipped
@@ -2581,7 +2592,11 @@ int asr_geom_grid_neighbors_fill(asr_hip_context* ctx, const u64* keys, i64 v, c
     NbBatch b = nb_one_grid(keys, v);
     b.idx[0] = idx;
     b.kidx[0] = kidx;
-    ASR_TRY(nb_key_maps(ctx, b, [] { return ASR_HIP_OK; }));
+    // (the same keys as the _count call before: the enlargement its key map needed; a larger table never loses a key.
+    // The note serves one _fill call: forgotten here, so that no later call on other keys at a reused address matches it)
+    const int grow0 = ctx->nb_grow_keys == keys && ctx->nb_grow_v == v ? ctx->nb_grow : 0;
+    ctx->nb_grow_keys = nullptr;
+    ASR_TRY(nb_key_maps(ctx, b, [] { return ASR_HIP_OK; }, grow0));
     k_neighbors_fill_batch<<<grid_for(v + 1, BLK), BLK, 0, ctx->stream>>>(b, rs, nullptr, nullptr, nullptr);
     ASR_CHECK_LAUNCH(ctx);
     return ASR_HIP_OK;
@@ -3124,7 +3139,10 @@ int asr_geom_precells(asr_hip_context* ctx, Arena& keep) {
     ASR_TRY(build_cell_table(ctx, pi.n, 1, pi.lsort, st, false, &keep));
     int host[16];
     ASR_TRY(read_flags(ctx, host));
-    if (host[1]) return ASR_HIP_OK;  // overflow: the query builds (and grows) its own table
+    if (host[1]) {  // overflow: the query builds (and grows) its own table
+        ++ctx->table_regrows;
+        return ASR_HIP_OK;
+    }
     pi.tab_grow = st.cell_grow;
     pi.tab_keys = st.tab.keys;
     pi.tab_mask = st.tab.mask;
@@ -3243,6 +3261,7 @@ int asr_geom_radius_count(asr_hip_context* ctx, const asr_octree_frame* frame, c
     if (host[1]) {  // retry with a table four times the size
         if (st.cell_grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "radius search cell table overflow");
         st.cell_grow += 2;
+        ++ctx->table_regrows;
         return asr_geom_radius_count(ctx, frame, pts, n, centers, sizes, v, rs, num_pairs, keep, radii, voxel_keys,
                                      lmin_hint, lmax_hint, pre);
     }
@@ -3283,9 +3302,21 @@ int asr_geom_radius_neighbor_count(asr_hip_context* ctx, const asr_octree_frame*
     if (n <= 0) return ASR_HIP_OK;
     if (n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "too many points for int32 indices");
     RadiusState st;
+    st.cell_grow = rstate(ctx).cell_grow;
     int host[16], lmin, lmax;
     ASR_TRY(query_level_range(ctx, frame, radii, n, &lmin, &lmax));
-    ASR_TRY(build_point_index(ctx, frame, pts, n, lmin, lmax, st, nullptr, false, false));
+    ArenaMark mark;
+    arena_mark(ctx->scratch, mark);
+    for (;;) {
+        ASR_TRY(build_point_index(ctx, frame, pts, n, lmin, lmax, st, nullptr, false, false));
+        ASR_TRY(read_flags(ctx, host));
+        if (!host[1]) break;
+        if (st.cell_grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "cell table overflow");
+        st.cell_grow += 2;  // lattice-like clouds crowd a few buckets (see TabProbe): a table four times the size
+        rstate(ctx).cell_grow = st.cell_grow;
+        ++ctx->table_regrows;
+        arena_rewind(ctx->scratch, mark);
+    }
     i64* counts = arena_alloc<i64>(ctx->scratch, n + 1);
     if (!counts) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
     k_radius_query<0, false><<<grid_for(n + 1, 4), BLK, 0, ctx->stream>>>(
@@ -3293,8 +3324,6 @@ int asr_geom_radius_neighbor_count(asr_hip_context* ctx, const asr_octree_frame*
     ASR_CHECK_LAUNCH(ctx);
     ASR_HIP_CHECK(ctx, hipMemcpyAsync(counts_out, counts, n * sizeof(i64), hipMemcpyDeviceToDevice,
                                       ctx->stream));
-    ASR_TRY(read_flags(ctx, host));
-    if (host[1]) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "cell table overflow");
     return ASR_HIP_OK;
 }
 
@@ -3330,6 +3359,7 @@ int asr_geom_attributes_at(asr_hip_context* ctx, const asr_octree_frame* frame, 
         if (st.cell_grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "radius search cell table overflow");
         st.cell_grow += 2;  // lattice-like clouds crowd a few buckets (see TabProbe): a table four times the size
         rstate(ctx).cell_grow = st.cell_grow;
+        ++ctx->table_regrows;
         arena_rewind(ctx->scratch, mark);
     }
     float* sattr = arena_alloc<float>(ctx->scratch, (size_t)(n + 1) * cp);
@@ -3376,8 +3406,20 @@ int asr_geom_knn(asr_hip_context* ctx, const asr_octree_frame* frame, const floa
     int lfine = 1;
     while (lfine < ASR_MAX_LEVEL - 1 && (i64(1) << (3 * lfine)) < n) ++lfine;
     RadiusState st;
+    st.cell_grow = rstate(ctx).cell_grow;
     int host[16];
-    ASR_TRY(build_point_index(ctx, frame, pts, n, 0, lfine, st));
+    ArenaMark mark;
+    arena_mark(ctx->scratch, mark);
+    for (;;) {  // the overflow is read before any kernel walks the table: one that lost keys misses neighbours
+        ASR_TRY(build_point_index(ctx, frame, pts, n, 0, lfine, st));
+        ASR_TRY(read_flags(ctx, host));
+        if (!host[1]) break;
+        if (st.cell_grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "cell table overflow");
+        st.cell_grow += 2;  // lattice-like clouds crowd a few buckets (see TabProbe): a table four times the size
+        rstate(ctx).cell_grow = st.cell_grow;
+        ++ctx->table_regrows;
+        arena_rewind(ctx->scratch, mark);
+    }
     st.lhash = lfine;
     // dense spots: a finest-level cell with thousands of points makes every one of them walk thousands of candidates.
     // Such clouds get their points sorted eight levels deeper, and the points of crowded cells start on a finer level.
@@ -3432,8 +3474,6 @@ int asr_geom_knn(asr_hip_context* ctx, const asr_octree_frame* frame, const floa
                                                        nullptr, 0);
         ASR_CHECK_LAUNCH(ctx);
     }
-    ASR_TRY(read_flags(ctx, host));
-    if (host[1]) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "cell table overflow");
     return ASR_HIP_OK;
 }
 
@@ -3458,6 +3498,7 @@ int asr_geom_nearest(asr_hip_context* ctx, const asr_octree_frame* frame, const 
         if (st.cell_grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "nearest point: cell table overflow");
         st.cell_grow += 2;  // lattice-like clouds crowd a few buckets (see TabProbe): a table four times the size
         rstate(ctx).cell_grow = st.cell_grow;
+        ++ctx->table_regrows;
         arena_rewind(ctx->scratch, mark);
     }
     st.lhash = lfine;

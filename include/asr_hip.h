@@ -82,7 +82,13 @@ int asr_hip_context_weights_changed(asr_hip_context* ctx);
  * on the tuning options: none of them skips work.
  * "search_half" (1): the aggregation search of asr_hip_implicit_build covers a voxel's ball with 4^3 half-size
  * cells for the rows with many candidates (2: for every voxel, 0: 3^3 full-size cells throughout).  get_option also answers the read-only "last_search_margin_pairs": pairs the last
- * such search found in the rounding margin of the half-size cells. */
+ * such search found in the rounding margin of the half-size cells.
+ * Read-only "table_regrows": the number of times a hash table of the geometry half (octree closure and key growth, voxel
+ * key maps of the neighbour lists, the cell tables of the searches -- the early table of the overlapped
+ * build that is dropped included) overflowed and was rebuilt four times the size, since the context was created; the
+ * auxiliary search context is summed in.  Cumulative: take differences around a call.  Lattice-aligned clouds cause it
+ * (many keys share the low 6 bits that choose the slot inside a table's 64-slot buckets); a grown cell table stays grown
+ * for the later searches of the context.  It is no entry of asr_hip_option_info. */
 int asr_hip_context_set_option(asr_hip_context* ctx, const char* name, int64_t value);
 int asr_hip_context_get_option(asr_hip_context* ctx, const char* name, int64_t* value);
 /* The table of tunables: name and built-in default of option `index` (0, 1, ... until ASR_HIP_EINVAL).  A context's defaults can
@@ -190,7 +196,11 @@ int asr_hip_unordered_set_order(const uint32_t* xs, int n, uint32_t* out);
 
 /* ---- a5: CreateLeafNeighborInformation (cpp/lib/grid.cpp:43-175) ---------------------- */
 /* keys: sorted unique voxel keys. count: fills row_splits[V+1] and returns the pair count;
- * fill: writes the CSR entries in ascending kernel-slot order. */
+ * fill: writes the CSR entries in ascending kernel-slot order.
+ * Both build the voxel key map.  The context notes the enlargement the map of the last count call needed ("table_regrows"
+ * above) with the keys' address and number; the next fill call on the same context with that address and number starts at
+ * that size, not at the smallest, and clears the note.  A fill call without such a note grows its map by itself; the
+ * results never depend on it.  The same holds for the row-list pair below. */
 int asr_hip_grid_neighbors_count(asr_hip_context* ctx, const uint64_t* keys_dev, int64_t v,
                                  int64_t* row_splits_out_dev, int64_t* num_pairs);
 int asr_hip_grid_neighbors_fill(asr_hip_context* ctx, const uint64_t* keys_dev, int64_t v,

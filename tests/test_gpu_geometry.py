@@ -27,6 +27,10 @@ def _cloud(kind, n, seed):
         pts = (g * np.float32(0.0625)).astype(np.float32)
         nrm = np.tile(np.float32([0, 0, 1]), (len(pts), 1))
         n = len(pts)
+    elif kind == "pitch4":  # 8^3 sites at a pitch of four level-5 cells of KDTree's frame: the cell tables overflow and regrow
+        import crowded_inputs
+        pts, nrm = crowded_inputs.lattice_sites(8, 9, 5, seed=seed, anchors=True)[:2]
+        n = len(pts)
     else:
         p, q = synth.scan_cloud(n, seed=seed, device="cpu", density_variance=10.0 if kind == "mixed" else 1.0)
         pts, nrm = p.numpy(), q.numpy()
@@ -248,7 +252,8 @@ def test_kdtree_prefilter_queries(gpu):
     """KDTree mirror (cpp/pybind/module.cpp:455-489): exact k-th neighbour radius, inlier vote and
     radius neighbour counts vs brute force"""
     import adaptivesurfacereconstruction as asr
-    for kind, n, seed in (("scan", 6000, 5), ("mixed", 4000, 6), ("sphere", 3000, 7), ("lattice", 1728, 8)):
+    for kind, n, seed in (("scan", 6000, 5), ("mixed", 4000, 6), ("sphere", 3000, 7), ("lattice", 1728, 8),
+                          ("pitch4", 4610, 9)):
         pts, nrm, rad, bb = _cloud(kind, n, seed)
         if kind == "sphere":
             pts[:50] = pts[50:100]  # duplicates: zero distances and ties
