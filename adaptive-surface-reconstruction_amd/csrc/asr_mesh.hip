@@ -65,9 +65,10 @@ __device__ inline bool crossing(const float* values, float thr, i64 a, i64 b) { 
     return (va.x < 0 && vb.x > 0) || (va.x > 0 && vb.x < 0);
 }
 
-// one thread per dual cell: active flag and number of distinct corner voxels
-__global__ void k_contour_active(const float* values, const i64* duals, i64 nd, float thr, i64* flag,
-                                 i64* npairs) {
+// one thread per dual cell: active flag and number of distinct corner voxels.  A cell with a corner outside
+// [0, nv) raises flags[4] and counts as inactive: no later kernel loads through its indices.
+__global__ void k_contour_active(const float* values, i64 nv, const i64* duals, i64 nd, float thr, i64* flag,
+                                 i64* npairs, int* flags) {
     i64 d = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (d > nd) return;
     if (d == nd) {
@@ -76,7 +77,17 @@ __global__ void k_contour_active(const float* values, const i64* duals, i64 nd, 
         return;
     }
     i64 c[8];
-    for (int k = 0; k < 8; ++k) c[k] = duals[d * 8 + k];
+    bool in_range = true;
+    for (int k = 0; k < 8; ++k) {
+        c[k] = duals[d * 8 + k];
+        in_range &= c[k] >= 0 && c[k] < nv;
+    }
+    if (!in_range) {
+        atomicOr(&flags[4], 1);
+        flag[d] = 0;
+        npairs[d] = 0;
+        return;
+    }
     bool act = false;
     for (int e = 0; e < 12; ++e) act |= crossing(values, thr, c[c_cube_edges[e][0]], c[c_cube_edges[e][1]]);
     int distinct = 0;
@@ -239,7 +250,9 @@ __global__ __launch_bounds__(BLK) void k_contour_edges(const float* values, cons
         if (n > ASR_USET_CAP) atomicOr(&flags[2], 1);
         return;
     }
-    if (n < 3 || n > ASR_USET_CAP) return;
+    // n == 2 emits nothing but is sorted all the same: the reference sorts before it looks at n (:360-369), and two
+    // cells without a common face end it there
+    if (n < 2 || n > ASR_USET_CAP) return;
     if (values[a * 2] > values[b * 2]) {  // :357-358 orient from the lower to the higher value
         i64 s = a;
         a = b;
@@ -286,6 +299,7 @@ __global__ __launch_bounds__(BLK) void k_contour_edges(const float* values, cons
         atomicOr(&flags[3], 1);
         return;
     }
+    if (n < 3) return;
     int32_t* out = tri + tri_off[t] * 3;
     if (n == 3) {
         out[0] = (int32_t)sorted[0];
@@ -998,22 +1012,27 @@ int asr_mesh_contour_count(asr_hip_context* ctx, const float* values, i64 num_va
     MESH_ALLOC(npairs, i64, num_duals + 1);
     MESH_ALLOC(voff, i64, num_duals + 1);
     MESH_ALLOC(poff, i64, num_duals + 1);
-    k_contour_active<<<grid_for(num_duals + 1, BLK), BLK, 0, s>>>(values, duals, num_duals, threshold, flag,
-                                                                   npairs);
+    k_contour_active<<<grid_for(num_duals + 1, BLK), BLK, 0, s>>>(values, num_values, duals, num_duals, threshold,
+                                                                   flag, npairs, ctx->d_flags);
     ASR_CHECK_LAUNCH(ctx);
     ASR_TRY(scan_counts(ctx, ctx->scratch, flag, voff, num_duals + 1));
     ASR_TRY(scan_counts(ctx, ctx->scratch, npairs, poff, num_duals + 1));
     i64 na = 0, np = 0;
     ASR_TRY(read_i64(ctx, voff + num_duals, &na));
     ASR_TRY(read_i64(ctx, poff + num_duals, &np));
-    st.kind = 1;
+    int host[16];
+    ASR_TRY(read_flags(ctx, host));
+    if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "contour: dual vertex index out of range");
     st.values = values;
     st.duals = duals;
     st.num_values = num_values;
     st.num_duals = num_duals;
     st.thr = threshold;
     st.num_active = na;
-    if (na == 0) return ASR_HIP_OK;
+    if (na == 0) {
+        st.kind = 1;
+        return ASR_HIP_OK;
+    }
     MESH_ALLOC(active, int32_t, na);
     MESH_ALLOC(pairs, u64, np);
     MESH_ALLOC(pairs_sorted, u64, np);
@@ -1041,12 +1060,12 @@ int asr_mesh_contour_count(asr_hip_context* ctx, const float* values, i64 num_va
     ASR_TRY(scan_counts(ctx, ctx->scratch, extra_cnt, extra_off, na * 3 + 1));
     ASR_TRY(read_i64(ctx, tri_off + na * 3, &st.num_tri));
     ASR_TRY(read_i64(ctx, extra_off + na * 3, &st.num_extra));
-    int host[16];
     ASR_TRY(read_flags(ctx, host));
     if (host[2])
         ASR_FAIL(ctx, ASR_HIP_ELOGIC, "contour: more than %d dual cells around one edge", ASR_USET_CAP);
     if (na + st.num_extra >= (i64(1) << 31) || st.num_tri >= (i64(1) << 31) / 3)
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "contour: mesh does not fit 32-bit indices");
+    st.kind = 1;  // only a count that succeeded may be filled
     st.active = active;
     st.vtx = vtx0;
     st.adj_rs = adj_rs;

@@ -167,7 +167,12 @@ int asr_hip_dual_cells_fill(asr_hip_context* ctx, int64_t* dual_vertex_indices_o
  * device pointers that must stay valid until the fill call.  count returns the mesh sizes, fill
  * writes vertices f32[M,3] (one per active dual cell in dual order, then the fan centres in
  * emission order) and triangles i32[T,3] in the reference's serial emission order, including the
- * corner order it derives from libstdc++'s unordered_set iteration (see csrc/asr_uset.h). */
+ * corner order it derives from libstdc++'s unordered_set iteration (see csrc/asr_uset.h).
+ * count checks on the device, before any load through them, that every dual vertex index lies in
+ * [0, num_values): ASR_HIP_EINVAL "contour: dual vertex index out of range" otherwise.  More than 29 active
+ * cells around one crossing edge (no face-balanced octree has more than 8) is ASR_HIP_ELOGIC from count; cells
+ * around an edge that cannot be ordered are the reference's "cannot sort duals", ASR_HIP_ELOGIC from fill.
+ * fill is refused after a count that failed. */
 int asr_hip_contour_count(asr_hip_context* ctx, const float* values_dev, int64_t num_values,
                           const int64_t* dual_vertex_indices_dev, int64_t num_duals,
                           const float* node_positions_dev, float value_threshold,

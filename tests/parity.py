@@ -214,7 +214,7 @@ SPHERE_MESH_PIN = (1113, 2258, "ce9b39826aeff585")
 def sphere_field(n, seed=0, noise=0.0):
     """analytic values on the adaptive grid of a sphere cloud: [signed distance to the unit sphere,
     |sdf| / voxel size]; `noise` (in voxel sizes) roughens the field so that fans, quads and
-    boundary edges all occur"""
+    boundary edges all occur -- of 2..8 cells round an edge, no more (tests/contour_cells.py goes to 29)"""
     from asr_hip import synth
     pts, _ = synth.sphere_cloud(n, seed)
     rad = synth.knn_radii(pts, 24)
