@@ -176,7 +176,8 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
                         density_percentile_threshold=10.0, point_radius_estimation_knn=24,
                         octree_max_depth=21, contouring_value_threshold=1.0,
                         keep_n_connected_components=2**63 - 1, minimum_component_size=3, *, weights=None,
-                        precision="f32", vertex_normals=False, point_attributes=None, simplify=0, smooth=0):
+                        precision="f32", vertex_normals=False, point_attributes=None, simplify=0, smooth=0,
+                        fill_holes=0):
     """module.cpp:58-109,291-346 -> asr::ReconstructSurface (cpp/lib/asr.cpp:95-349): pre-filter,
     implicit values, dual contouring, component filter; every stage on the MI355X.
     `weights` (keyword only) replaces the reference's bundled model.pt, see _load_weights.
@@ -193,8 +194,12 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
     (ImplicitPipeline.mesh); it runs before vertex_normals and point_attributes, which describe the final vertices.
     `smooth` (keyword only): n > 0 runs n iterations of Taubin smoothing (asr_hip.ops.mesh_smooth with its defaults:
     lambda 0.5, mu -0.53, rims smoothed along themselves) after the component filter and after simplify, also before
-    vertex_normals and point_attributes."""
+    vertex_normals and point_attributes.
+    `fill_holes` (keyword only): m > 0 closes every simple boundary rim of at most m edges (3 <= m <= 2^20) with a fan
+    around the mean of its vertices (asr_hip.ops.mesh_fill_holes), after simplify and before smooth; longer rims, the
+    outer border of an open scan among them, stay open."""
     from asr_hip.pipeline import ImplicitPipeline
+    fill_holes = _ops.check_fill_arguments(fill_holes) if fill_holes != 0 else 0
     simplify = int(simplify)
     if simplify < 0:
         raise ValueError("simplify must be >= 0")
@@ -247,7 +252,8 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
     points_dev, radii_dev = torch.from_numpy(points).to(dev), torch.from_numpy(radii).to(dev)
     pipe.forward(points_dev, torch.from_numpy(normals).to(dev), radii_dev, bb_min, bb_max)
     v, t = pipe.mesh(contouring_value_threshold, keep_n_connected_components, minimum_component_size,
-                     **({"simplify": simplify} if simplify else {}), **({"smooth": smooth} if smooth else {}))
+                     **({"simplify": simplify} if simplify else {}), **({"smooth": smooth} if smooth else {}),
+                     **({"fill_holes": fill_holes} if fill_holes else {}))
     result = {"vertices": v.cpu().numpy(), "triangles": t.cpu().numpy()}
     if vertex_normals:
         _, grad = pipe.query(v, gradient=True)
@@ -335,6 +341,24 @@ def smooth_mesh(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, boundary=
     v = _ops.mesh_smooth(torch.from_numpy(vertices).to(dev), torch.from_numpy(triangles).to(dev), iterations, lam, mu,
                          boundary)
     return {"vertices": v.cpu().numpy(), "triangles": triangles}
+
+
+def fill_mesh_holes(vertices, triangles, max_edges):
+    """Not in the reference's module.  Closes the small holes of any triangle mesh (asr_hip.ops.mesh_fill_holes): every
+    simple boundary rim of at most `max_edges` edges (3..2^20) gets a hub vertex at the mean of its vertices and one
+    triangle per rim edge (a rim of three edges: one triangle, no hub).  Longer rims, rims that touch in a vertex and rims
+    whose triangles disagree about the orientation stay open.
+    -> {'vertices': f32 [V + hubs,3], 'triangles': i32 [T + new,3], 'rims', 'filled', 'too_long', 'not_simple',
+    'new_vertices', 'new_triangles': int}; the input vertices and triangles come first, unchanged."""
+    max_edges = _ops.check_fill_arguments(max_edges)
+    vertices = _f32(vertices, "vertices", "[V,3]", 2, 3)
+    triangles = np.ascontiguousarray(triangles, dtype=np.int32)
+    if triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError("triangles must have shape [T,3]")
+    dev = torch.device("cuda")
+    v, t, report = _ops.mesh_fill_holes(torch.from_numpy(vertices).to(dev), torch.from_numpy(triangles).to(dev), max_edges,
+                                        return_report=True)
+    return {"vertices": v.cpu().numpy(), "triangles": t.cpu().numpy(), **report}
 
 
 def mesh_topology(triangles, num_vertices=None):

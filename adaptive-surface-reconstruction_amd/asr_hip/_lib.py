@@ -140,6 +140,11 @@ class MeshTopology(ctypes.Structure):
         "nonmanifold_edges", "inconsistent_edges", "components", "boundary_loops", "euler")]
 
 
+class MeshFillReport(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int64) for name in (
+        "rims", "filled", "too_long", "not_simple", "new_vertices", "new_triangles")]
+
+
 # every symbol declared in include/asr_hip.h (tests/test_abi.py checks the list against the header)
 EXPORTS = [
     "asr_hip_context_create", "asr_hip_context_destroy", "asr_hip_context_set_stream",
@@ -160,6 +165,7 @@ EXPORTS = [
     "asr_hip_point_attributes_at", "asr_hip_nearest_point", "asr_hip_mesh_sample",
     "asr_hip_mesh_simplify_count", "asr_hip_mesh_simplify_fill",
     "asr_hip_mesh_edges_count", "asr_hip_mesh_edges_fill", "asr_hip_mesh_topology", "asr_hip_mesh_smooth",
+    "asr_hip_mesh_fill_holes_count", "asr_hip_mesh_fill_holes_fill",
     "asr_hip_implicit_build",
     "asr_hip_implicit_network", "asr_hip_implicit_aggregate", "asr_hip_implicit_forward", "asr_hip_implicit_get",
     "asr_hip_implicit_stage_ms", "asr_hip_implicit_query",
@@ -191,7 +197,8 @@ def load():
         for name, cls in (("asr_octree_frame", OctreeFrame), ("asr_sparse_conv_args", SparseConvArgs),
                           ("asr_weight", Weight), ("asr_implicit_params", ImplicitParams),
                           ("asr_implicit_sizes", ImplicitSizes), ("asr_shard_comm", ShardComm),
-                          ("asr_shard_stats", ShardStats), ("asr_mesh_topology", MeshTopology)):
+                          ("asr_shard_stats", ShardStats), ("asr_mesh_topology", MeshTopology),
+                          ("asr_mesh_fill_report", MeshFillReport)):
             if lib.asr_hip_struct_size(name.encode()) != ctypes.sizeof(cls):
                 raise AsrHipError("ABI mismatch: struct %s has a different size in libasr_hip.so"
                                   % name)
@@ -210,7 +217,11 @@ def load():
         lib.asr_hip_mesh_topology.argtypes = [vp, vp, i64, i64, ctypes.POINTER(MeshTopology)]
         lib.asr_hip_mesh_smooth.argtypes = [vp, vp, i64, vp, i64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_int, vp]
-        for name in ("asr_hip_mesh_edges_count", "asr_hip_mesh_edges_fill", "asr_hip_mesh_topology", "asr_hip_mesh_smooth"):
+        lib.asr_hip_mesh_fill_holes_count.argtypes = [vp, vp, i64, vp, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
+                                                      ctypes.POINTER(MeshFillReport)]
+        lib.asr_hip_mesh_fill_holes_fill.argtypes = [vp, vp, vp]
+        for name in ("asr_hip_mesh_edges_count", "asr_hip_mesh_edges_fill", "asr_hip_mesh_topology", "asr_hip_mesh_smooth",
+                     "asr_hip_mesh_fill_holes_count", "asr_hip_mesh_fill_holes_fill"):
             getattr(lib, name).restype = ctypes.c_int
         _lib = lib
     return _lib

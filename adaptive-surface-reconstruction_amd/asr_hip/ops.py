@@ -919,6 +919,44 @@ def mesh_smooth(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, boundary=
     return out
 
 
+FILL_MAX_EDGES = 1 << 20
+
+
+def check_fill_arguments(max_edges):
+    """-> max_edges as an int or ValueError; no GPU involved"""
+    if isinstance(max_edges, bool) or int(max_edges) != max_edges or not 3 <= int(max_edges) <= FILL_MAX_EDGES:
+        raise ValueError("max_edges must be an integer in 3..%d" % FILL_MAX_EDGES)
+    return int(max_edges)
+
+
+def mesh_fill_holes(vertices, triangles, max_edges, return_report=False, ctx=None):
+    """Closes the small holes of a triangle mesh (asr_hip_mesh_fill_holes_count / _fill; the contract is in
+    include/asr_hip.h): every simple boundary rim of at most `max_edges` (3..2^20) edges gets a hub vertex at the mean of
+    its vertices and one triangle per rim edge, oriented like the triangle on the edge's other side; a rim of three edges
+    gets one triangle and no hub.  Rims that are longer (the outer border of an open scan), that touch another rim in a
+    vertex or whose triangles disagree about the orientation stay open.
+    -> (vertices f32 [V + hubs,3], triangles int32 [T + new,3]): the input arrays come first, unchanged.
+    return_report=True adds a dict of ints: rims, filled, too_long, not_simple, new_vertices, new_triangles."""
+    max_edges = check_fill_arguments(max_edges)
+    vertices = _dev(vertices, torch.float32)
+    triangles = _dev(triangles, torch.int32)
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must have shape [V,3]")
+    if triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError("triangles must have shape [T,3]")
+    dev = _same_device(vertices, triangles)
+    ctx = ctx or context(dev)
+    nvo, nto, report = i64(0), i64(0), _lib.MeshFillReport()
+    ctx.call("asr_hip_mesh_fill_holes_count", ptr(vertices), i64(vertices.shape[0]), ptr(triangles),
+             i64(triangles.shape[0]), i64(max_edges), ctypes.byref(nvo), ctypes.byref(nto), ctypes.byref(report))
+    v2 = torch.empty((nvo.value, 3), dtype=torch.float32, device=dev)
+    t2 = torch.empty((nto.value, 3), dtype=torch.int32, device=dev)
+    ctx.call("asr_hip_mesh_fill_holes_fill", ptr(v2), ptr(t2))
+    if return_report:
+        return v2, t2, {name: int(getattr(report, name)) for name, _ in _lib.MeshFillReport._fields_}
+    return v2, t2
+
+
 def decode_mlp_at(code, shifts, w1, b1, w2, b2, w3, rows=None, voxel_sizes=None, gradient=False):
     """UNet5.decode(shifts, code[rows]) (net_definitions_torch.py:655-666) -> values [M,2]; with gradient=True
     (values, grad [M,3]) where grad is decode_with_gradient's d values[:,0] / d shift (:668-686, unscaled).

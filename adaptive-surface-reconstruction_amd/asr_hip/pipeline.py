@@ -250,14 +250,17 @@ class ImplicitPipeline:
         return ops.dual_cells(self.device, ctx=self.ctx)
 
     def mesh(self, contouring_value_threshold=1.0, keep_n_connected_components=2**63 - 1,
-             minimum_component_size=3, values=None, simplify=0, smooth=0):
+             minimum_component_size=3, values=None, simplify=0, smooth=0, fill_holes=0):
         """contouring + component filter on the last forward (cpp/lib/asr.cpp:338-346) ->
         (vertices f32[M,3], triangles i32[T,3]) on the GPU.  simplify=k > 0 (not in the reference): the filtered mesh
         is then simplified in the forward's frame (ops.mesh_simplify): all vertices inside one cell k levels above the
         grid-0 leaf that contains them become one vertex (level max(0, leaf level - k); a vertex outside every leaf
         stays alone).  The simplified mesh is not filtered again.  smooth=n > 0 (not in the reference): n iterations of
-        Taubin smoothing with the defaults of ops.mesh_smooth, after the component filter and after simplify."""
+        Taubin smoothing with the defaults of ops.mesh_smooth, after the component filter and after simplify.
+        fill_holes=m > 0 (not in the reference): every simple boundary rim of at most m edges is closed by a centroid fan
+        (ops.mesh_fill_holes), after simplify and before smooth, so that the smoother relaxes the fans."""
         from . import ops
+        m = ops.check_fill_arguments(fill_holes) if fill_holes != 0 else 0
         self._stream()
         if values is None:
             values = self.get("values")
@@ -273,6 +276,9 @@ class ImplicitPipeline:
             frame = _lib.frame_init(*self._bb)
             with torch.cuda.device(self.device):
                 v, t = ops.mesh_simplify(frame, v, t, levels=self.simplify_levels(v, k), ctx=self.ctx)
+        if m > 0:
+            with torch.cuda.device(self.device):
+                v, t = ops.mesh_fill_holes(v, t, m, ctx=self.ctx)
         if n > 0:
             with torch.cuda.device(self.device):
                 v = ops.mesh_smooth(v, t, iterations=n, ctx=self.ctx)

@@ -227,6 +227,22 @@ def average_colors(colors, vertex_map, num_out):
     return np.rint(total / np.maximum(count, 1)).astype(np.uint8)
 
 
+def hub_attributes(values, triangles, num_in, num_out):
+    """per-vertex values [num_in,C] (normals f32 or colours uint8) of a mesh carried through a hole filling
+    (ops.mesh_fill_holes): the input vertices keep theirs; every hub, a vertex >= num_in, gets the mean of the values of
+    the rim vertices its new triangles (b, a, hub) name, colours rounded to nearest -> [num_out,C] of values' dtype"""
+    values = np.asarray(values)
+    tri = np.asarray(triangles, np.int64).reshape(-1, 3)
+    fans = tri[tri[:, 2] >= num_in]
+    num_hubs = num_out - num_in
+    total = np.zeros((num_hubs, values.shape[1]))
+    np.add.at(total, fans[:, 2] - num_in, values[fans[:, 1]].astype(np.float64))
+    mean = total / np.maximum(np.bincount(fans[:, 2] - num_in, minlength=num_hubs), 1)[:, None]
+    if values.dtype == np.uint8:
+        mean = np.rint(mean)
+    return np.concatenate([values, mean.astype(values.dtype)])
+
+
 def read_surface(path):
     """A surface to compare against (asrtool --compare): -> (vertices f32 [N,3], triangles i32 [T,3] or None, normals
     f32 [N,3] or None).  A file with a non-empty face element is a triangle mesh in the layout write_mesh produces; one

@@ -3,10 +3,11 @@ reference (cpp/bin/main.cpp:114-177: `asrtool --in point_cloud.ply --out mesh.pl
 `--third-party-notices`) on top of adaptivesurfacereconstruction.reconstruct_surface.
 
     python adaptive-surface-reconstruction_amd/asrtool.py --in scan.ply --out mesh.ply [--weights model.pt] [--precision NAME]
-                                                          [--normals] [--colors] [--simplify K] [--smooth N]
+                                                          [--normals] [--colors] [--simplify K] [--smooth N] [--fill-holes N]
     python adaptive-surface-reconstruction_amd/asrtool.py --compare mesh.ply reference.ply [--samples N] [--thresholds a,b,...] [--seed S]
     python adaptive-surface-reconstruction_amd/asrtool.py --decimate mesh.ply out.ply --cell SIZE
     python adaptive-surface-reconstruction_amd/asrtool.py --smooth-mesh mesh.ply out.ply [--iterations N] [--boundary free|pinned|along]
+    python adaptive-surface-reconstruction_amd/asrtool.py --fill-mesh mesh.ply out.ply --max-edges N
     python adaptive-surface-reconstruction_amd/asrtool.py --topology mesh.ply
 
 The reference bundles its network as <resource dir>/model.pt (cpp/lib/asr.cpp:138-139); here the weights come
@@ -31,6 +32,11 @@ Options:
               normals and colours then describe the simplified vertices
     --smooth N  Taubin smoothing of the mesh, N iterations (1 <= N <= 1000), after --simplify; normals and colours then
               describe the smoothed vertices
+    --fill-holes N  Closes every simple boundary rim of at most N edges (3 <= N <= 1048576) with a fan around the mean of its
+              vertices, after --simplify and before --smooth; longer rims, the outer border of an open scan among them, stay open
+    --fill-mesh MESH.ply OUT.ply --max-edges N  Instead of reconstructing: closes the holes of at most N edges of an existing
+              mesh and prints one JSON line with the counts (rims, filled, too_long, not_simple, new_vertices, new_triangles).
+              Each new hub vertex gets the mean of the normals and colours of its rim
     --smooth-mesh MESH.ply OUT.ply  Instead of reconstructing: Taubin smoothing of an existing mesh (lambda 0.5, mu -0.53).
               Vertex normals and colours are carried over unchanged
     --iterations N  --smooth-mesh: iterations (default 10, 0 <= N <= 1000)
@@ -178,6 +184,49 @@ def _smooth_mesh(argv):
     return 0
 
 
+def _max_edges(text):
+    """the N of --fill-holes / --max-edges, or None when it is no integer in 3..2^20"""
+    try:
+        n = int(text)
+    except (TypeError, ValueError):
+        return None
+    return n if 3 <= n <= 1 << 20 else None
+
+
+def _fill_mesh(argv):
+    """--fill-mesh MESH.ply OUT.ply --max-edges N: one JSON line, 0; a message on stderr and 1 (before any GPU work) when
+    something is wrong"""
+    import json
+    i = argv.index("--fill-mesh")
+    paths = argv[i + 1:i + 3]
+    if len(paths) < 2 or any(p.startswith("--") for p in paths):
+        sys.stderr.write("asrtool: --fill-mesh needs two files: MESH.ply OUT.ply\n")
+        return 1
+    max_edges = _max_edges(_option(argv, "--max-edges"))
+    if max_edges is None:
+        sys.stderr.write("asrtool: --fill-mesh needs --max-edges N, an integer, 3 <= N <= 1048576\n")
+        return 1
+    if not os.path.isfile(paths[0]):
+        sys.stderr.write("asrtool: --fill-mesh: no such file: %s\n" % paths[0])
+        return 1
+    from asr_hip import ply
+    try:
+        v, t, normals, colors = ply.read_mesh(paths[0], with_normals=True, with_colors=True)
+    except (ValueError, IndexError, OSError) as e:
+        sys.stderr.write("asrtool: --fill-mesh: cannot read %s as a mesh: %s\n" % (paths[0], e))
+        return 1
+    import adaptivesurfacereconstruction as asr
+    result = asr.fill_mesh_holes(v, t, max_edges)
+    v2, t2 = result.pop("vertices"), result.pop("triangles")
+    if normals is not None:
+        normals = ply.hub_attributes(normals, t2, len(v), len(v2))
+    if colors is not None:
+        colors = ply.hub_attributes(colors, t2, len(v), len(v2))
+    ply.write_mesh(paths[1], v2, t2, normals=normals, colors=colors)
+    print(json.dumps(result))
+    return 0
+
+
 def _topology(argv):
     """--topology MESH.ply: one JSON line, 0; a message on stderr and 1 (before any GPU work) when something is wrong"""
     import json
@@ -216,6 +265,8 @@ def main(argv=None):
         return _decimate(argv)
     if "--smooth-mesh" in argv:
         return _smooth_mesh(argv)
+    if "--fill-mesh" in argv:
+        return _fill_mesh(argv)
     if "--topology" in argv:
         return _topology(argv)
     inp, out = _option(argv, "--in"), _option(argv, "--out")
@@ -245,6 +296,12 @@ def main(argv=None):
         if not 1 <= smooth <= 1000:
             sys.stderr.write("asrtool: --smooth takes a number of iterations N, 1 <= N <= 1000\n")
             return 1
+    fill_holes = 0
+    if "--fill-holes" in argv:  # before any GPU work
+        fill_holes = _max_edges(_option(argv, "--fill-holes"))
+        if fill_holes is None:
+            sys.stderr.write("asrtool: --fill-holes takes a number of rim edges N, 3 <= N <= 1048576\n")
+            return 1
     from asr_hip import ply
     colors = None
     if "--colors" in argv:  # before any GPU work: a cloud without colours is an error
@@ -261,6 +318,8 @@ def main(argv=None):
         extra["simplify"] = simplify
     if smooth:
         extra["smooth"] = smooth
+    if fill_holes:
+        extra["fill_holes"] = fill_holes
     result = asr.reconstruct_surface(points, normals, radii, weights=_option(argv, "--weights"), precision=precision,
                                      vertex_normals="--normals" in argv, **extra)
     if colors is not None:

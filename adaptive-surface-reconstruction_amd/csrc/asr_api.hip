@@ -107,6 +107,7 @@ size_t asr_hip_struct_size(const char* name) {
     if (!strcmp(name, "asr_shard_comm")) return sizeof(asr_shard_comm);
     if (!strcmp(name, "asr_shard_stats")) return sizeof(asr_shard_stats);
     if (!strcmp(name, "asr_mesh_topology")) return sizeof(asr_mesh_topology);
+    if (!strcmp(name, "asr_mesh_fill_report")) return sizeof(asr_mesh_fill_report);
     return 0;
 }
 
@@ -782,6 +783,25 @@ int asr_hip_mesh_smooth(asr_hip_context* ctx, const float* vertices, int64_t num
     if (boundary < 0 || boundary > 2) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: boundary mode %d is not in 0..2", boundary);
     return asr_mesh_smooth(ctx, vertices, num_vertices, triangles, num_triangles, iterations, lambda, mu, boundary,
                            vertices_out);
+}
+int asr_hip_mesh_fill_holes_count(asr_hip_context* ctx, const float* vertices, int64_t num_vertices, const int32_t* triangles,
+                                  int64_t num_triangles, int64_t max_edges, int64_t* num_vertices_out,
+                                  int64_t* num_triangles_out, asr_mesh_fill_report* report) {
+    CTX_GUARD(ctx);
+    if (!num_vertices_out || !num_triangles_out || !report || (num_vertices > 0 && !vertices) ||
+        (num_triangles > 0 && !triangles))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes_count: null argument");
+    if (num_vertices < 0 || num_triangles < 0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes_count: negative size");
+    if (num_vertices >= (i64(1) << 31) || num_triangles >= (i64(1) << 31) / 3)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes_count: mesh does not fit 32-bit indices");
+    if (max_edges < 3 || max_edges > (i64(1) << 20))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes_count: max_edges %lld is not in 3..2^20", (long long)max_edges);
+    return asr_mesh_fill_holes_count(ctx, vertices, num_vertices, triangles, num_triangles, (int)max_edges,
+                                     num_vertices_out, num_triangles_out, report);
+}
+int asr_hip_mesh_fill_holes_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out) {
+    CTX_GUARD(ctx);
+    return asr_mesh_fill_holes_fill(ctx, vertices_out, triangles_out);
 }
 
 }  // extern "C"

@@ -521,6 +521,10 @@ int asr_mesh_edges_fill(asr_hip_context* ctx, int32_t* edges, int32_t* uses, int
 int asr_mesh_topology_report(asr_hip_context* ctx, const int32_t* triangles, i64 nt, i64 nv, asr_mesh_topology* out);
 int asr_mesh_smooth(asr_hip_context* ctx, const float* vertices, i64 nv, const int32_t* triangles, i64 nt, int iterations,
                     double lambda, double mu, int boundary, float* vertices_out);
+// centroid fans over the simple rims of at most max_edges edges (asr_hip_mesh_fill_holes_count / _fill)
+int asr_mesh_fill_holes_count(asr_hip_context* ctx, const float* vertices, i64 nv, const int32_t* triangles, i64 nt,
+                              int max_edges, i64* nv_out, i64* nt_out, asr_mesh_fill_report* report);
+int asr_mesh_fill_holes_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out);
 void asr_mesh_release(asr_hip_context* ctx);
 
 int asr_conv_agg_importance(asr_hip_context* ctx, const float* compat, const float* dist, i64 n,

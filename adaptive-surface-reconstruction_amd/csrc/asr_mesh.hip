@@ -29,7 +29,7 @@ __constant__ int c_cube_faces[6][4] = {{0, 1, 3, 2}, {4, 6, 7, 5}, {1, 5, 7, 3},
 __constant__ int c_owned_edges[3][2] = {{0, 1}, {1, 3}, {1, 5}};  // edge subset {0,1,9}
 
 struct MeshState {
-    int kind = 0;  // 1 = contour, 2 = components, 3 = simplify, 4 = edge table
+    int kind = 0;  // 1 = contour, 2 = components, 3 = simplify, 4 = edge table, 5 = fill holes
     // contour
     const float* values = nullptr;
     const i64* duals = nullptr;
@@ -57,6 +57,16 @@ struct MeshState {
     const u64* e_keys = nullptr;   // sorted side keys
     const i64* e_start = nullptr;  // first side of every edge (num_edges+1)
     const i64* e_count = nullptr;  // the number of edges, on the device
+    // fill holes (in_vtx, in_tri, nv, nt as above; nv_out - nv hubs, nt_out - nt new triangles)
+    i64 f_rim_vertices = 0, f_long = 0;  // vertices on filled rims; filled rims longer than FILL_CUT
+    const u64* f_keys = nullptr;         // (rim id << 32) | vertex of the vertices on filled rims, sorted
+    const int* f_len = nullptr;          // per rim id: its number of boundary edges
+    const int* f_succ = nullptr;         // tail -> head of the boundary edge that leaves a vertex
+    const int* f_start = nullptr;        // per filled rim id: its first entry in f_keys
+    const i64* f_hub_off = nullptr;      // exclusive scan over the rim ids: hubs (nv+1)
+    const i64* f_tri_off = nullptr;      // the same for the new triangles
+    const int32_t* f_hub_rims = nullptr;   // hub -> rim id
+    const int32_t* f_long_rims = nullptr;  // the filled rims a whole wave sums
 };
 
 __device__ inline bool crossing(const float* values, float thr, i64 a, i64 b) {  // :81-111
@@ -975,6 +985,166 @@ __global__ __launch_bounds__(BLK) void k_smooth_step_long(const double* __restri
     pos_store(pout, i, px, py, pz);
 }
 
+// ------------------------------------------------------------------------------------------
+// Hole filling (contract: include/asr_hip.h).  The boundary edges (uses == 1) are directed tail -> head
+// as their one triangle runs through them; a rim is a set of the union-find over the boundary edges alone and its id the
+// set's root, its smallest vertex.  A rim is simple when every vertex of it leaves and enters exactly once; the simple
+// rims of at most max_edges edges get a fan: the sorted keys (rim id << 32) | vertex give the ascending vertex order
+// the hub sums in and the order of the new triangles.
+// ------------------------------------------------------------------------------------------
+constexpr int FILL_CUT = SMOOTH_CUT;  // rims longer than this are summed by a whole wave (k_fill_hub_long)
+enum { FILL_RIMS = 0, FILL_FILLED, FILL_TOO_LONG, FILL_NOT_SIMPLE, FILL_RIM_VERTICES, FILL_COUNTERS };
+
+__global__ void k_fill_degrees(const int32_t* edges, const int32_t* uses, const int32_t* forward, const i64* ecount, i64 cap,
+                               int* out_deg, int* in_deg, int* succ) {
+    const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= cap || e >= *ecount) return;
+    if (uses[e] != 1) return;
+    const int lo = edges[2 * e], hi = edges[2 * e + 1];
+    const bool fw = forward[e] == 1;
+    const int tail = fw ? lo : hi, head = fw ? hi : lo;
+    atomicAdd(&out_deg[tail], 1);
+    atomicAdd(&in_deg[head], 1);
+    succ[tail] = head;  // one writer per tail on a simple rim; the others are never walked
+}
+// per boundary vertex: its rim, the rim's length (the edges that leave its vertices) and whether it is not simple
+__global__ void k_fill_rim_stats(int* parent, const uint8_t* on_bnd, const int* out_deg, const int* in_deg, i64 nv,
+                                 int* root_of, int* len, int* bad) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    if (!on_bnd[i]) {
+        root_of[i] = -1;
+        return;
+    }
+    const int r = uf_find(parent, (int)i);
+    root_of[i] = r;
+    const int od = out_deg[i];
+    if (od != 1 || in_deg[i] != 1) atomicOr(&bad[r], 1);
+    if (od > 1) atomicAdd(&len[r], od);
+    // the vertices that leave once: one atomic per distinct rim in the wave (an outer border has 10^5 of them)
+    bool todo = od == 1;
+    while (todo) {
+        const int lead = __builtin_amdgcn_readfirstlane(r);
+        const unsigned long long same = __ballot(r == lead);
+        if (r == lead) {
+            if ((int)(threadIdx.x & 63) == __ffsll((long long)same) - 1) atomicAdd(&len[lead], __popcll(same));
+            todo = false;
+        }
+    }
+}
+// the decision per rim id (i <= nv; the entries of the vertices that are no rim id, and entry nv, are 0)
+__global__ void k_fill_select(const uint8_t* on_bnd, const int* root_of, const int* len, const int* bad, i64 nv,
+                              int max_edges, uint8_t* filled_rim, i64* hub_flag, i64* tri_count, i64* long_flag, ull* cnt) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > nv) return;
+    if (i == nv) {
+        hub_flag[i] = tri_count[i] = long_flag[i] = 0;
+        return;
+    }
+    const bool rim = on_bnd[i] && root_of[i] == (int)i;
+    const int n = rim ? len[i] : 0;
+    const bool simple = rim && !bad[i];
+    const bool filled = simple && n <= max_edges;
+    filled_rim[i] = filled ? 1 : 0;
+    hub_flag[i] = filled && n >= 4 ? 1 : 0;
+    tri_count[i] = filled ? (n == 3 ? 1 : n) : 0;
+    long_flag[i] = filled && n > FILL_CUT ? 1 : 0;
+    wave_count(&cnt[FILL_RIMS], rim);
+    wave_count(&cnt[FILL_FILLED], filled);
+    wave_count(&cnt[FILL_TOO_LONG], simple && !filled);
+    wave_count(&cnt[FILL_NOT_SIMPLE], rim && !simple);
+    if (filled) atomicAdd(&cnt[FILL_RIM_VERTICES], (ull)n);
+}
+// (rim id << 32) | vertex for the vertices of the filled rims -- the only vertices whose coordinates are read -- and
+// nv << 32, which sorts behind them, for all others
+__global__ void k_fill_keys(const float* vtx, const int* root_of, const uint8_t* filled_rim, i64 nv, u64* keys, int* flags) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    const int r = root_of[i];
+    u64 key = (u64)nv << 32;
+    if (r >= 0 && filled_rim[r]) {
+        const float x = vtx[3 * i], y = vtx[3 * i + 1], z = vtx[3 * i + 2];
+        if (!(isfinite(x) && isfinite(y) && isfinite(z))) atomicOr(&flags[7], 1);
+        key = ((u64)(u32)r << 32) | (u64)(u32)i;
+    }
+    keys[i] = key;
+}
+__global__ void k_fill_starts(const u64* keys, i64 nv, int* start) {
+    const i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nv) return;
+    const i64 rim = (i64)(keys[p] >> 32);
+    if (rim >= nv) return;
+    if (p == 0 || (i64)(keys[p - 1] >> 32) != rim) start[rim] = (int)p;
+}
+__global__ void k_fill_lists(const i64* hub_off, const i64* long_off, i64 nv, int32_t* hub_rims, int32_t* long_rims) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    if (hub_off[i + 1] > hub_off[i]) hub_rims[hub_off[i]] = (int32_t)i;
+    if (long_off[i + 1] > long_off[i]) long_rims[long_off[i]] = (int32_t)i;
+}
+// the hub of a rim of at most FILL_CUT vertices, one thread per hub: a sequential sum in ascending vertex order
+__global__ __launch_bounds__(BLK) void k_fill_hub(const float* __restrict__ vtx, const u64* __restrict__ keys,
+                                                  const int* __restrict__ len, const int* __restrict__ start,
+                                                  const int32_t* __restrict__ hub_rims, i64 nhubs, float* __restrict__ hubs) {
+    const i64 h = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= nhubs) return;
+    const int rim = hub_rims[h];
+    const int n = len[rim];
+    if (n > FILL_CUT) return;  // k_fill_hub_long writes this hub
+    const u64* row = keys + start[rim];
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (int k = 0; k < n; ++k) {
+        const i64 v = (i64)(u32)row[k];
+        sx += (double)vtx[3 * v], sy += (double)vtx[3 * v + 1], sz += (double)vtx[3 * v + 2];
+    }
+    const double d = (double)n;
+    hubs[3 * h] = (float)(sx / d), hubs[3 * h + 1] = (float)(sy / d), hubs[3 * h + 2] = (float)(sz / d);
+}
+// the longer rims, one wave per rim: the shape of k_smooth_step_long
+__global__ __launch_bounds__(BLK) void k_fill_hub_long(const float* __restrict__ vtx, const u64* __restrict__ keys,
+                                                       const int* __restrict__ len, const int* __restrict__ start,
+                                                       const i64* __restrict__ hub_off, const int32_t* __restrict__ long_rims,
+                                                       i64 nlong, float* __restrict__ hubs) {
+    const i64 w = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (w >= nlong) return;  // whole waves leave together
+    const int rim = long_rims[w];
+    const int n = len[rim];
+    const u64* row = keys + start[rim];
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (int k = lane; k < n; k += 64) {
+        const i64 v = (i64)(u32)row[k];
+        sx += (double)vtx[3 * v], sy += (double)vtx[3 * v + 1], sz += (double)vtx[3 * v + 2];
+    }
+    for (int m = 32; m >= 1; m >>= 1) {
+        sx += __shfl_xor(sx, m);
+        sy += __shfl_xor(sy, m);
+        sz += __shfl_xor(sz, m);
+    }
+    if (lane != 0) return;
+    const i64 h = hub_off[rim];
+    const double d = (double)n;
+    hubs[3 * h] = (float)(sx / d), hubs[3 * h + 1] = (float)(sy / d), hubs[3 * h + 2] = (float)(sz / d);
+}
+// one thread per vertex of a filled rim, in key order: the triangle across the boundary edge that leaves it
+__global__ void k_fill_emit(const u64* keys, i64 nrv, const int* len, const int* start, const int* succ, const i64* hub_off,
+                            const i64* tri_off, i64 nv, int32_t* tri) {
+    const i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nrv) return;
+    const u64 k = keys[p];
+    const int rim = (int)(k >> 32), a = (int)(u32)k;
+    const i64 r = p - start[rim];
+    if (len[rim] == 3) {  // no hub: (m, p, s) with p -> m -> s
+        if (r != 0) return;
+        const int s = succ[a], q = succ[s];
+        int32_t* o = tri + 3 * tri_off[rim];
+        o[0] = a, o[1] = q, o[2] = s;
+        return;
+    }
+    int32_t* o = tri + 3 * (tri_off[rim] + r);
+    o[0] = succ[a], o[1] = a, o[2] = (int32_t)(nv + hub_off[rim]);
+}
+
 MeshState& mstate(asr_hip_context* ctx) {
     if (!ctx->mesh_state) ctx->mesh_state = new MeshState();
     return *(MeshState*)ctx->mesh_state;
@@ -1556,5 +1726,145 @@ int asr_mesh_smooth(asr_hip_context* ctx, const float* vertices, i64 nv, const i
         }
     k_smooth_store<<<grid_for(nv, BLK), BLK, 0, s>>>(pos[cur], nv, vertices_out);
     ASR_CHECK_LAUNCH(ctx);
+    return ASR_HIP_OK;
+}
+
+int asr_mesh_fill_holes_count(asr_hip_context* ctx, const float* vertices, i64 nv, const int32_t* triangles, i64 nt,
+                              int max_edges, i64* nv_out, i64* nt_out, asr_mesh_fill_report* report) {
+    MeshState& st = mstate(ctx);
+    st = MeshState();
+    memset(report, 0, sizeof(*report));
+    *nv_out = nv;
+    *nt_out = nt;
+    st.in_vtx = vertices;
+    st.in_tri = triangles;
+    st.nv = st.nv_out = nv;
+    st.nt = st.nt_out = nt;
+    if (nt == 0) {
+        st.kind = 5;
+        return ASR_HIP_OK;
+    }
+    if (nv == 0)  // every corner is out of range
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes: triangle index out of range");
+    ASR_TRY(ensure_flags(ctx));
+    ctx->scratch.reset();
+    hipStream_t s = ctx->stream;
+    ASR_TRY(fresh_flags(ctx));
+    MESH_ALLOC(cnt, ull, FILL_COUNTERS);
+    ASR_HIP_CHECK(ctx, hipMemsetAsync(cnt, 0, FILL_COUNTERS * sizeof(ull), s));
+    EdgeTable et;
+    ASR_TRY(edge_table(ctx, triangles, nt, nv, nullptr, et));
+    // as in the topology report the number of edges stays on the device: launches for its upper bound, the sides
+    const i64 cap = et.nq;
+    MESH_ALLOC(edges, int32_t, 2 * cap);
+    MESH_ALLOC(uses, int32_t, cap);
+    MESH_ALLOC(forward, int32_t, cap);
+    MESH_ALLOC(parent, int, nv);
+    MESH_ALLOC(ints, int, 6 * nv);  // out_deg, in_deg, len, bad, succ, start: zeroed together
+    int *out_deg = ints, *in_deg = ints + nv, *len = ints + 2 * nv, *bad = ints + 3 * nv, *succ = ints + 4 * nv,
+        *start = ints + 5 * nv;
+    MESH_ALLOC(root_of, int, nv);
+    MESH_ALLOC(marks, uint8_t, 2 * nv);  // on the boundary; rim id of a filled rim
+    uint8_t *on_bnd = marks, *filled_rim = marks + nv;
+    MESH_ALLOC(hub_flag, i64, nv + 1);
+    MESH_ALLOC(tri_count, i64, nv + 1);
+    MESH_ALLOC(long_flag, i64, nv + 1);
+    MESH_ALLOC(hub_off, i64, nv + 1);
+    MESH_ALLOC(tri_off, i64, nv + 1);
+    MESH_ALLOC(long_off, i64, nv + 1);
+    MESH_ALLOC(keys, u64, nv);
+    MESH_ALLOC(keys_s, u64, nv);
+    // a rim with a hub has at least 4 vertices, a long one more than FILL_CUT, and rims share no vertex
+    MESH_ALLOC(hub_rims, int32_t, nv / 4 + 1);
+    MESH_ALLOC(long_rims, int32_t, nv / (FILL_CUT + 1) + 1);
+    ASR_HIP_CHECK(ctx, hipMemsetAsync(ints, 0, (size_t)(6 * nv) * sizeof(int), s));
+    ASR_HIP_CHECK(ctx, hipMemsetAsync(marks, 0, (size_t)(2 * nv), s));
+    k_adj_edge_out<<<grid_for(cap, BLK), BLK, 0, s>>>(et.keys, et.start, et.count, cap, edges, uses, forward);
+    ASR_CHECK_LAUNCH(ctx);
+    k_uf_init<<<grid_for(nv, BLK), BLK, 0, s>>>(parent, nv);
+    ASR_CHECK_LAUNCH(ctx);
+    k_uf_link_edges<<<grid_for(cap, BLK), BLK, 0, s>>>(edges, uses, et.count, cap, 1, parent, on_bnd);
+    ASR_CHECK_LAUNCH(ctx);
+    k_fill_degrees<<<grid_for(cap, BLK), BLK, 0, s>>>(edges, uses, forward, et.count, cap, out_deg, in_deg, succ);
+    ASR_CHECK_LAUNCH(ctx);
+    k_fill_rim_stats<<<grid_for(nv, BLK), BLK, 0, s>>>(parent, on_bnd, out_deg, in_deg, nv, root_of, len, bad);
+    ASR_CHECK_LAUNCH(ctx);
+    k_fill_select<<<grid_for(nv + 1, BLK), BLK, 0, s>>>(on_bnd, root_of, len, bad, nv, max_edges, filled_rim, hub_flag,
+                                                        tri_count, long_flag, cnt);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(scan_counts(ctx, ctx->scratch, hub_flag, hub_off, nv + 1));
+    ASR_TRY(scan_counts(ctx, ctx->scratch, tri_count, tri_off, nv + 1));
+    ASR_TRY(scan_counts(ctx, ctx->scratch, long_flag, long_off, nv + 1));
+    k_fill_keys<<<grid_for(nv, BLK), BLK, 0, s>>>(vertices, root_of, filled_rim, nv, keys, ctx->d_flags);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(sort_keys(ctx, ctx->scratch, keys, keys_s, nv, 32 + bits_for(nv + 1)));
+    k_fill_starts<<<grid_for(nv, BLK), BLK, 0, s>>>(keys_s, nv, start);
+    ASR_CHECK_LAUNCH(ctx);
+    k_fill_lists<<<grid_for(nv, BLK), BLK, 0, s>>>(hub_off, long_off, nv, hub_rims, long_rims);
+    ASR_CHECK_LAUNCH(ctx);
+    // the one read-back: counters, sizes and flags
+    ull h[FILL_COUNTERS];
+    i64 sizes[3] = {0, 0, 0};
+    int host[16];
+    ASR_HIP_CHECK(ctx, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, s));
+    ASR_HIP_CHECK(ctx, hipMemcpyAsync(&sizes[0], hub_off + nv, sizeof(i64), hipMemcpyDeviceToHost, s));
+    ASR_HIP_CHECK(ctx, hipMemcpyAsync(&sizes[1], tri_off + nv, sizeof(i64), hipMemcpyDeviceToHost, s));
+    ASR_HIP_CHECK(ctx, hipMemcpyAsync(&sizes[2], long_off + nv, sizeof(i64), hipMemcpyDeviceToHost, s));
+    ASR_TRY(read_flags(ctx, host));
+    if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes: triangle index out of range");
+    if (host[7]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes: a vertex of a filled rim is not finite");
+    if (nv + sizes[0] >= (i64(1) << 31) || nt + sizes[1] >= (i64(1) << 31) / 3)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes: the filled mesh does not fit 32-bit indices");
+    report->rims = (i64)h[FILL_RIMS];
+    report->filled = (i64)h[FILL_FILLED];
+    report->too_long = (i64)h[FILL_TOO_LONG];
+    report->not_simple = (i64)h[FILL_NOT_SIMPLE];
+    report->new_vertices = sizes[0];
+    report->new_triangles = sizes[1];
+    st.kind = 5;
+    st.nv_out = *nv_out = nv + sizes[0];
+    st.nt_out = *nt_out = nt + sizes[1];
+    st.f_rim_vertices = (i64)h[FILL_RIM_VERTICES];
+    st.f_long = sizes[2];
+    st.f_keys = keys_s;
+    st.f_len = len;
+    st.f_succ = succ;
+    st.f_start = start;
+    st.f_hub_off = hub_off;
+    st.f_tri_off = tri_off;
+    st.f_hub_rims = hub_rims;
+    st.f_long_rims = long_rims;
+    return ASR_HIP_OK;
+}
+
+int asr_mesh_fill_holes_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out) {
+    MeshState& st = mstate(ctx);
+    if (st.kind != 5)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes_fill must follow the matching mesh_fill_holes_count call");
+    st.kind = 0;
+    hipStream_t s = ctx->stream;
+    if (st.nv > 0)
+        ASR_HIP_CHECK(ctx, hipMemcpyAsync(vertices_out, st.in_vtx, (size_t)st.nv * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (st.nt > 0)
+        ASR_HIP_CHECK(ctx, hipMemcpyAsync(triangles_out, st.in_tri, (size_t)st.nt * 3 * sizeof(int32_t),
+                                          hipMemcpyDeviceToDevice, s));
+    const i64 nhubs = st.nv_out - st.nv;
+    if (nhubs > 0) {
+        float* hubs = vertices_out + 3 * st.nv;
+        k_fill_hub<<<grid_for(nhubs, BLK), BLK, 0, s>>>(st.in_vtx, st.f_keys, st.f_len, st.f_start, st.f_hub_rims, nhubs, hubs);
+        ASR_CHECK_LAUNCH(ctx);
+        if (st.f_long > 0) {
+            k_fill_hub_long<<<grid_for(st.f_long * 64, BLK), BLK, 0, s>>>(st.in_vtx, st.f_keys, st.f_len, st.f_start,
+                                                                          st.f_hub_off, st.f_long_rims, st.f_long, hubs);
+            ASR_CHECK_LAUNCH(ctx);
+        }
+    }
+    if (st.nt_out > st.nt) {
+        k_fill_emit<<<grid_for(st.f_rim_vertices, BLK), BLK, 0, s>>>(st.f_keys, st.f_rim_vertices, st.f_len, st.f_start,
+                                                                     st.f_succ, st.f_hub_off, st.f_tri_off, st.nv,
+                                                                     triangles_out + 3 * st.nt);
+        ASR_CHECK_LAUNCH(ctx);
+    }
+    ASR_HIP_CHECK(ctx, hipStreamSynchronize(s));
     return ASR_HIP_OK;
 }

@@ -604,6 +604,46 @@ int asr_hip_mesh_topology(asr_hip_context* ctx, const int32_t* triangles_dev, in
 int asr_hip_mesh_smooth(asr_hip_context* ctx, const float* vertices_dev, int64_t num_vertices,
                         const int32_t* triangles_dev, int64_t num_triangles, int iterations, double lambda, double mu,
                         int boundary, float* vertices_out_dev);
+/* ---- hole filling: centroid fans over small boundary rims (not in the reference).
+ * The contract, which tests/mesh_fill_ref.py restates in numpy; degenerate triangles, uses, forward and boundary edges
+ * (uses == 1) are those of the mesh adjacency section above.
+ *   The one use of a boundary edge runs a -> b inside its triangle: a is the edge's TAIL and b its HEAD (forward == 1
+ *     means lo -> hi, otherwise hi -> lo).
+ *   A RIM is a connected component of the graph of the boundary edges alone (what boundary_loops counts).  Its id is
+ *     its smallest vertex index and its length n the number of its boundary edges.
+ *   A rim is SIMPLE when each of its vertices is the tail of exactly one and the head of exactly one of its boundary
+ *     edges: it is then one consistently directed cycle of n >= 3 vertices.  Rims that touch in a vertex, rims through
+ *     a vertex with three or more boundary edges and rims whose triangles disagree about the orientation are not
+ *     simple and are left alone.
+ *   A rim is FILLED when it is simple and n <= max_edges.  max_edges must lie in 3..2^20 (else ASR_HIP_EINVAL): the
+ *     outer border of an open scan is a rim too, and the cap is what keeps it open.
+ *   Output vertices: the input vertices first, bits unchanged (unused ones stay), then one HUB per filled rim with
+ *     n >= 4 in ascending rim id.  The hub is the mean of the rim's vertices: an f64 sum of the f32 coordinates in
+ *     ascending vertex index (rims of up to 128 vertices sequentially; longer rims as the 64 interleaved partial sums,
+ *     lane l taking the entries l, l + 64, ..., added pairwise xor 32, 16, ... 1, of asr_hip_mesh_smooth), divided by
+ *     n in f64 without contraction and rounded once to f32.  No float atomics.
+ *   Output triangles: all input triangles first, unchanged and in order (degenerate ones stay), then the new ones
+ *     ordered by rim id and inside a rim by ascending tail a.  A rim with n >= 4 gets one triangle (b, a, hub) per
+ *     boundary edge a -> b: it crosses the edge the other way, so the edge becomes a consistent 2-use edge.  A rim
+ *     with n == 3 gets no hub and the one triangle (m, p, s): m is the rim id, p -> m and m -> s its boundary edges.
+ *     (A mesh of a single triangle so becomes a two-sided pillow.)
+ *   Report: rims (== boundary_loops of asr_hip_mesh_topology), filled, too_long (simple, n > max_edges), not_simple
+ *     (whatever its length), new_vertices (hubs), new_triangles.  Every filled rim raises the Euler characteristic by
+ *     exactly 1; an edge-manifold, oriented mesh with simple rims only and max_edges >= its longest rim comes out
+ *     watertight.
+ * Count / fill pair like asr_hip_mesh_simplify_*: _count reads the report, the sizes and the error flags back once;
+ * scratch comes from the context arena and stays valid until _fill, which must be the next mesh call on the context
+ * and also copies the input arrays (the outputs must not overlap the inputs).
+ * ASR_HIP_EINVAL: a corner out of range ("out of range"); a vertex ON A FILLED RIM that is not finite -- no other
+ * vertex is read; a result that no longer fits the sizes above.  num_triangles == 0, or no boundary at all, copies the
+ * input and gives a zero report.  The same inputs give the same bits on every run. */
+typedef struct asr_mesh_fill_report {
+    int64_t rims, filled, too_long, not_simple, new_vertices, new_triangles;
+} asr_mesh_fill_report;
+int asr_hip_mesh_fill_holes_count(asr_hip_context* ctx, const float* vertices_dev, int64_t num_vertices,
+                                  const int32_t* triangles_dev, int64_t num_triangles, int64_t max_edges,
+                                  int64_t* num_vertices_out, int64_t* num_triangles_out, asr_mesh_fill_report* report);
+int asr_hip_mesh_fill_holes_fill(asr_hip_context* ctx, float* vertices_out_dev, int32_t* triangles_out_dev);
 /* (asr_hip_implicit_query, the whole-path query on the last forward, is declared after asr_hip_implicit_stage_ms) */
 
 /* ---- whole path: the section of asr::ReconstructSurface between the pre-filter and the
