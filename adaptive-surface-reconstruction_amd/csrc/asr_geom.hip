@@ -177,7 +177,7 @@ __global__ void k_point_keys(asr_octree_frame f, const float* pts, const float* 
 // a4: octree node set.  Nodes live in an open-addressing hash set (membership) AND in an append
 // only list of sibling groups (8 consecutive keys, first sibling first): the list gives the
 // BalanceFaces frontiers and the final node array without ever scanning the (mostly empty) table.
-// cnt[0] = list entries (multiple of 8), cnt[1] = overflow flag, cnt[9] = root inserted.
+// cnt[F_ENTRIES] = list entries (multiple of 8), cnt[F_OVERFLOW] = overflow flag, cnt[F_ROOT] = root inserted (asr_prim.h).
 // ------------------------------------------------------------------------------------------
 // insert the sibling group of `a` and all missing ancestor groups (+ root).
 // The thread that wins the CAS on a group's first sibling creates the other seven and
@@ -188,14 +188,14 @@ __device__ inline void insert_with_ancestors(const HashTab& t, u64 a, int* cnt, 
     while (true) {
         if (a == 1) {
             int r = tab_insert(t, 1);
-            if (r == 1) cnt[9] = 1;
-            if (r < 0) cnt[1] = 1;
+            if (r == 1) cnt[F_ROOT] = 1;
+            if (r < 0) cnt[F_OVERFLOW] = 1;
             return;
         }
         u64 first = a & ~u64(7);
         int r = tab_insert(t, first);
         if (r < 0) {
-            cnt[1] = 1;
+            cnt[F_OVERFLOW] = 1;
             return;
         }
         // One list append per WAVE iteration: the lanes of the wave that are in this iteration of the loop and created
@@ -205,26 +205,26 @@ __device__ inline void insert_with_ancestors(const HashTab& t, u64 a, int* cnt, 
         const unsigned long long m = __ballot(created);
         if (!created) return;
         for (int j = 1; j < 8; ++j)
-            if (tab_insert(t, first + j) < 0) cnt[1] = 1;
+            if (tab_insert(t, first + j) < 0) cnt[F_OVERFLOW] = 1;
         const int leader = __builtin_ctzll(m);
         int base = 0;
-        if (lane == leader) base = atomicAdd(&cnt[0], 8 * __popcll(m));
+        if (lane == leader) base = atomicAdd(&cnt[F_ENTRIES], 8 * __popcll(m));
         base = __shfl(base, leader, 64);
         const int pos = base + 8 * __popcll(m & ((1ull << lane) - 1));
         if (pos + 8 <= list_cap) {
             for (int j = 0; j < 8; ++j) list[pos + j] = first + j;
         } else {
-            cnt[1] = 1;
+            cnt[F_OVERFLOW] = 1;
         }
         a >>= 3;
     }
 }
 
-// cnt[13] = number of significant bits of the longest key in the node list (cnt[0] entries; the list is radix-sorted on
+// cnt[F_KEY_BITS] = number of significant bits of the longest key in the node list (cnt[F_ENTRIES] entries; the list is radix-sorted on
 // those bits only).  A pass of its own over the list: the same test inside the insertion kernels, next to their atomics
-// on cnt[0], made them 2.6x slower.
+// on cnt[F_ENTRIES], made them 2.6x slower.
 __global__ void k_list_key_bits(const u64* list, int list_cap, int* cnt) {
-    const int n = min(cnt[0], list_cap);
+    const int n = min(cnt[F_ENTRIES], list_cap);
     int bits = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const u64 k = list[i];
@@ -232,7 +232,7 @@ __global__ void k_list_key_bits(const u64* list, int list_cap, int* cnt) {
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) bits = max(bits, __shfl_xor(bits, o, 64));
-    if ((threadIdx.x & 63) == 0 && bits) atomicMax(&cnt[13], bits);
+    if ((threadIdx.x & 63) == 0 && bits) atomicMax(&cnt[F_KEY_BITS], bits);
 }
 
 __global__ void k_octree_insert_points(asr_octree_frame f, const float* pts, const float* radii,
@@ -242,7 +242,7 @@ __global__ void k_octree_insert_points(asr_octree_frame f, const float* pts, con
     u64 key = 0;
     if (i < n) {
         if (!(isfinite(pts[3 * i]) && isfinite(pts[3 * i + 1]) && isfinite(pts[3 * i + 2]) && isfinite(radii[i])))
-            cnt[11] = 1;  // rejected by the host: the reference has undefined behaviour on such input
+            cnt[F_NONFINITE] = 1;  // rejected by the host: the reference has undefined behaviour on such input
         else
             key = point_key(f, pts, radii, i, radius_scale, max_depth);
     }
@@ -264,19 +264,19 @@ __global__ void k_grow_init(asr_octree_frame f, const float* pts, const float* r
     i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (!(isfinite(pts[3 * i]) && isfinite(pts[3 * i + 1]) && isfinite(pts[3 * i + 2]) && isfinite(radii[i]))) {
-        cnt[11] = 1;
+        cnt[F_NONFINITE] = 1;
         return;
     }
     const u64 key = point_key(f, pts, radii, i, radius_scale, max_depth);
     if (key == 0) return;
     const int r = tab_insert(t, key);
-    if (r < 0) cnt[1] = 1;
+    if (r < 0) cnt[F_OVERFLOW] = 1;
     if (r == 1) {
-        const int pos = atomicAdd(&cnt[0], 1);
+        const int pos = atomicAdd(&cnt[F_ENTRIES], 1);
         if (pos < list_cap)
             list[pos] = key;
         else
-            cnt[1] = 1;
+            cnt[F_OVERFLOW] = 1;
     }
 }
 __device__ inline bool tab_has_child(const HashTab& t, u64 key) {
@@ -320,13 +320,13 @@ __global__ void k_grow_insert(HashTab t, u64* list, int lo, int count, const u64
         key = first + sj;
     }
     const int r = tab_insert(t, key);
-    if (r < 0) cnt[1] = 1;
+    if (r < 0) cnt[F_OVERFLOW] = 1;
     if (r == 1) {
-        const int pos = atomicAdd(&cnt[0], 1);
+        const int pos = atomicAdd(&cnt[F_ENTRIES], 1);
         if (pos < list_cap)
             list[pos] = key;
         else
-            cnt[1] = 1;
+            cnt[F_OVERFLOW] = 1;
     }
 }
 // closure over an explicit key list (the grown set) instead of the points
@@ -389,7 +389,7 @@ __global__ void k_map_build(const u64* keys, i64 v, HashTab t, int* cnt) {
     u64 slot;
     int r = tab_insert(t, keys[i], &slot);
     if (r < 0)
-        cnt[1] = 1;
+        cnt[F_OVERFLOW] = 1;
     else
         t.vals[slot] = (int32_t)i;
 }
@@ -437,7 +437,7 @@ __global__ void k_check_rows(const int32_t* rows, i64 nrows, i64 v, int* cnt, in
     const i64 r = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     if (r >= nrows) return;
     const i64 q = rows[r];
-    if (q < 0 || q >= v || (r > 0 && rows[r - 1] >= q)) cnt[3] = 1;  // in range, strictly ascending
+    if (q < 0 || q >= v || (r > 0 && rows[r - 1] >= q)) cnt[F_BAD_KEY] = 1;  // in range, strictly ascending
     else if (mark) mark[q] = 1;
 }
 __global__ void k_check_keys(const u64* keys, i64 n, int* cnt) {
@@ -445,7 +445,7 @@ __global__ void k_check_keys(const u64* keys, i64 n, int* cnt) {
     if (i >= n) return;
     const u64 k = keys[i];
     // a location code: leading bit at position 3 * level, level <= ASR_MAX_LEVEL (0 is the tables' empty sentinel)
-    if (k == 0 || (63 - __clzll((long long)k)) % 3 != 0) cnt[3] = 1;
+    if (k == 0 || (63 - __clzll((long long)k)) % 3 != 0) cnt[F_BAD_KEY] = 1;
 }
 
 // The lists of ALL grids of a hierarchy in one launch each (asr_geom_neighbors_build_batch; the stand-alone operators
@@ -482,7 +482,7 @@ __global__ void k_map_build_batch(NbBatch b, int* cnt) {
     if (i >= b.v[j]) return;
     u64 slot;
     if (tab_insert(b.tab[j], b.keys[j][i], &slot) < 0)
-        cnt[1] = 1;
+        cnt[F_OVERFLOW] = 1;
     else
         b.tab[j].vals[slot] = (int32_t)i;
 }
@@ -708,7 +708,7 @@ __global__ void k_point_codes(asr_octree_frame f, const float* pts, i64 n, u64* 
                               int32_t* ids, int* cnt) {
     i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     if (i >= n) return;
-    if (!(isfinite(pts[3 * i]) && isfinite(pts[3 * i + 1]) && isfinite(pts[3 * i + 2]))) cnt[11] = 1;
+    if (!(isfinite(pts[3 * i]) && isfinite(pts[3 * i + 1]) && isfinite(pts[3 * i + 2]))) cnt[F_NONFINITE] = 1;
     int x, y, z;
     frame_coord(f, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], ASR_MAX_LEVEL, x, y, z);
     const int lim = (1 << ASR_MAX_LEVEL) - 1;
@@ -738,16 +738,10 @@ __device__ inline int query_level(const asr_octree_frame& f, float r) {
     while (lev < ASR_MAX_LEVEL && f.voxel_size[lev + 1] >= r) ++lev;
     return lev;
 }
-// grid-stride + block reduction: one atomic pair per BLOCK (same-address atomics retire at ~88 / us, one
-// per wave was 0.9 ms for 2.6 M voxels)
-__global__ __launch_bounds__(256) void k_query_levels(asr_octree_frame f, const float* sizes, i64 v, int* cnt) {
+// block reduction of the level range of a 256-thread block: one atomic pair per BLOCK (same-address atomics retire at
+// ~88 / us, one per wave was 0.9 ms for 2.6 M voxels)
+__device__ __forceinline__ void block_level_range(int lo, int hi, int* cnt) {
     __shared__ int s_lo[4], s_hi[4];
-    int lo = ASR_MAX_LEVEL, hi = 0;
-    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < v; i += (i64)gridDim.x * blockDim.x) {
-        const int l = query_level(f, sizes[i]);
-        lo = min(lo, l);
-        hi = max(hi, l);
-    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         lo = min(lo, __shfl_xor(lo, o, 64));
@@ -759,9 +753,19 @@ __global__ __launch_bounds__(256) void k_query_levels(asr_octree_frame f, const 
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        atomicMin(&cnt[6], min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3])));
-        atomicMax(&cnt[7], max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3])));
+        atomicMin(&cnt[F_LEVEL_MIN], min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3])));
+        atomicMax(&cnt[F_LEVEL_MAX], max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3])));
     }
+}
+// grid-stride loop over the query sizes
+__global__ __launch_bounds__(256) void k_query_levels(asr_octree_frame f, const float* sizes, i64 v, int* cnt) {
+    int lo = ASR_MAX_LEVEL, hi = 0;
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < v; i += (i64)gridDim.x * blockDim.x) {
+        const int l = query_level(f, sizes[i]);
+        lo = min(lo, l);
+        hi = max(hi, l);
+    }
+    block_level_range(lo, hi, cnt);
 }
 // boundaries of the sorted code array: cell (prefix,level) starts / ends at i
 template <bool COUNT_ONLY>
@@ -791,13 +795,13 @@ __global__ __launch_bounds__(256) void k_cell_bounds(const u64* codes, i64 n, in
                 u64 slot;
                 if (has_a) {
                     if (tab_insert(t, pa | marker, &slot) < 0)
-                        cnt[1] = 1;
+                        cnt[F_OVERFLOW] = 1;
                     else
                         end[slot] = (int32_t)i;
                 }
                 if (has_b) {
                     if (tab_insert(t, pb | marker, &slot) < 0)
-                        cnt[1] = 1;
+                        cnt[F_OVERFLOW] = 1;
                     else
                         start[slot] = (int32_t)i;
                 }
@@ -809,7 +813,7 @@ __global__ __launch_bounds__(256) void k_cell_bounds(const u64* codes, i64 n, in
         for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o, 64);
         if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = local;
         __syncthreads();
-        if (threadIdx.x == 0) atomicAdd(&cnt[8], s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]);
+        if (threadIdx.x == 0) atomicAdd(&cnt[F_CELLS], s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]);
         if (level_cnt && threadIdx.x <= ASR_MAX_LEVEL && s_lvl[threadIdx.x]) atomicAdd(&level_cnt[threadIdx.x], s_lvl[threadIdx.x]);
     }
 }
@@ -1177,7 +1181,6 @@ __global__ void k_attr_permute(const float* attr, const int32_t* ids, i64 n, int
 }
 // levels of the cell table: the finest any query starts on (k = 0) and the coarsest any can widen to (k = max_widen)
 __global__ __launch_bounds__(256) void k_attr_levels(asr_octree_frame f, const float* sizes, i64 m, float widen, int* cnt) {
-    __shared__ int s_lo[4], s_hi[4];
     int lo = ASR_MAX_LEVEL, hi = 0;
     for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < m; i += (i64)gridDim.x * blockDim.x) {
         const float s = sizes[i];
@@ -1185,20 +1188,7 @@ __global__ __launch_bounds__(256) void k_attr_levels(asr_octree_frame f, const f
         hi = max(hi, query_level(f, s));
         lo = min(lo, query_level(f, s * widen));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = min(lo, __shfl_xor(lo, o, 64));
-        hi = max(hi, __shfl_xor(hi, o, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_lo[threadIdx.x >> 6] = lo;
-        s_hi[threadIdx.x >> 6] = hi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicMin(&cnt[6], min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3])));
-        atomicMax(&cnt[7], max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3])));
-    }
+    block_level_range(lo, hi, cnt);
 }
 template <int CP>
 __global__ __launch_bounds__(256) void k_attr_blend(asr_octree_frame f, const float4* __restrict__ sorted,
@@ -2161,15 +2151,15 @@ __global__ void k_rg_masks(RowGroupBatch b, u64* masks, HashTab t, int* cnt) {
         const i64* rs = b.rs[j];
         const uint8_t* kidx = b.kidx[j];
         for (i64 p = rs[r]; p < rs[r + 1]; ++p) m |= u64(1) << (kidx[p] & 63);
-        if (tab_insert_shared(t, (m >> 1) + 1) < 0) cnt[1] = 1;
+        if (tab_insert_shared(t, (m >> 1) + 1) < 0) cnt[F_OVERFLOW] = 1;
     }
     masks[e] = m;
 }
-// the set's keys as a dense list (any order) with their slots; cnt[2] = how many
+// the set's keys as a dense list (any order) with their slots; cnt[F_MASKS] = how many
 __global__ void k_rg_mask_collect(HashTab t, u64* list, int32_t* slot_of, int* cnt) {
     const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
     const u64 k = i <= t.mask ? t.keys[i] : 0;
-    const int o = block_append(k != 0, cnt + 2);
+    const int o = block_append(k != 0, cnt + F_MASKS);
     if (k && o < RG_MAX_MASKS) {
         list[o] = k;
         slot_of[o] = (int32_t)i;
@@ -2180,7 +2170,7 @@ __global__ void k_rg_mask_collect(HashTab t, u64* list, int32_t* slot_of, int* c
 // whose waves share that CU's issue slots -- on the critical chain of the build.)
 __global__ __launch_bounds__(256) void k_rg_mask_ranks(HashTab t, const u64* list, const int32_t* slot_of, const int* cnt) {
     __shared__ u64 s_key[2048];
-    const int n = cnt[2];
+    const int n = cnt[F_MASKS];
     if (n > RG_MAX_MASKS) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (blockIdx.x * blockDim.x >= n) return;
@@ -2287,7 +2277,7 @@ __global__ void k_dual_fill(const u64* leaves, i64 v, HashTab t, const i64* offs
             int r = -2;
             while (k != 0 && (r = node_lookup(t, k)) == -2) k >>= 3;  // grid.cpp:429-441
             if (k == 0 || r < 0) {
-                cnt[1] = 1;  // "invalid key after searching for node" / "found node is not a leaf"
+                cnt[F_DUAL_KEY] = 1;  // "invalid key after searching for node" / "found node is not a leaf"
                 r = -1;
             }
             out[o * 8 + j] = r;
@@ -2326,7 +2316,7 @@ int asr_geom_point_keys(asr_hip_context* ctx, const asr_octree_frame* frame, con
 // Octree::Grow: the grown key set of `grow_steps` iterations as a device list in `arena` (see k_grow_*)
 static int grow_keys(asr_hip_context* ctx, Arena& arena, const asr_octree_frame* frame, const float* pts, const float* radii,
                      i64 n, float radius_scale, int max_depth, int grow_steps, u64** keys_out, i64* count_out) {
-    int host[16];
+    HostFlags host;
     u64 cap = next_pow2((u64)std::max<i64>(i64(1) << 16, 8 * n));
     for (int attempt = 0; attempt < 6; ++attempt, cap <<= 2) {
         if (attempt) ++ctx->table_regrows;
@@ -2340,11 +2330,11 @@ static int grow_keys(asr_hip_context* ctx, Arena& arena, const asr_octree_frame*
                                                              ctx->d_flags, list, lcap);
         ASR_CHECK_LAUNCH(ctx);
         ASR_TRY(read_flags(ctx, host));
-        if (host[3]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "octree: extra_keys holds a value that is no location code (0 or a leading "
+        if (host[F_BAD_KEY]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "octree: extra_keys holds a value that is no location code (0 or a leading "
                                                    "bit that is not at 3 * level)");
-        if (host[11]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "octree: points / radii contain non-finite values");
-        bool overflow = host[1] != 0;
-        int lo = 0, hi = host[0];
+        if (host[F_NONFINITE]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "octree: points / radii contain non-finite values");
+        bool overflow = host[F_OVERFLOW] != 0;
+        int lo = 0, hi = host[F_ENTRIES];
         for (int it = 0; it < grow_steps && !overflow && hi > lo; ++it) {
             const int count = hi - lo;
             if ((i64)count * 14 >= (i64(1) << 31) || (u64)(hi + (i64)count * 14) > (u64)lcap) {
@@ -2359,13 +2349,13 @@ static int grow_keys(asr_hip_context* ctx, Arena& arena, const asr_octree_frame*
                                                                                   lcap);
             ASR_CHECK_LAUNCH(ctx);
             ASR_TRY(read_flags(ctx, host));
-            overflow = host[1] != 0;
+            overflow = host[F_OVERFLOW] != 0;
             lo = hi;
-            hi = host[0];
+            hi = host[F_ENTRIES];
         }
         if (overflow) continue;
         *keys_out = list;
-        *count_out = host[0];
+        *count_out = host[F_ENTRIES];
         return ASR_HIP_OK;
     }
     ASR_FAIL(ctx, ASR_HIP_ELOGIC, "octree grow: hash table overflow");
@@ -2392,7 +2382,7 @@ int asr_geom_octree_build(asr_hip_context* ctx, const asr_octree_frame* frame, c
         ASR_TRY(grow_keys(ctx, grow_arena, frame, pts, radii, n, radius_scale, max_depth, grow_steps, &grown, &num_grown));
     // nodes of a scan are ~0.3 n; the table must stay at most half full (cap / 2 list entries), else retry 4x larger
     u64 cap = next_pow2((u64)std::max<i64>(i64(1) << 16, 2 * std::max(std::max(n, 4 * num_grown), num_extra)));
-    int host[16];
+    HostFlags host;
     for (int attempt = 0; attempt < 7; ++attempt, cap <<= 2) {
         if (attempt) ++ctx->table_regrows;
         ctx->scratch.reset();
@@ -2424,9 +2414,9 @@ int asr_geom_octree_build(asr_hip_context* ctx, const asr_octree_frame* frame, c
         k_list_key_bits<<<256, BLK, 0, ctx->stream>>>(list, lcap, ctx->d_flags);  // (balancing adds no longer keys)
         ASR_CHECK_LAUNCH(ctx);
         ASR_TRY(read_flags(ctx, host));
-        if (host[11]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "octree: points / radii contain non-finite values");
-        bool overflow = host[1] != 0 || (u64)host[0] * 2 > cap;
-        int lo = 0, hi = host[0];
+        if (host[F_NONFINITE]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "octree: points / radii contain non-finite values");
+        bool overflow = host[F_OVERFLOW] != 0 || (u64)host[F_ENTRIES] * 2 > cap;
+        int lo = 0, hi = host[F_ENTRIES];
         while (balance && !overflow && hi > lo) {
             int ngroups = (hi - lo) / 8;
             k_balance_classify<<<grid_for(ngroups, BLK), BLK, 0, ctx->stream>>>(t, list, lo, ngroups, flag);
@@ -2435,21 +2425,21 @@ int asr_geom_octree_build(asr_hip_context* ctx, const asr_octree_frame* frame, c
                     t, list, lo, ngroups, flag, ctx->d_flags, lcap);
             ASR_CHECK_LAUNCH(ctx);
             ASR_TRY(read_flags(ctx, host));
-            overflow = host[1] != 0 || (u64)host[0] * 2 > cap;
+            overflow = host[F_OVERFLOW] != 0 || (u64)host[F_ENTRIES] * 2 > cap;
             lo = hi;
-            hi = host[0];
+            hi = host[F_ENTRIES];
         }
         if (overflow) continue;
-        i64 num_nodes = (i64)host[0] + (host[9] ? 1 : 0);
+        i64 num_nodes = (i64)host[F_ENTRIES] + (host[F_ROOT] ? 1 : 0);
         ctx->leaf_lmin = ctx->leaf_lmax = -1;
         if (num_nodes == 0) {
             ctx->num_nodes = ctx->num_leaves = 0;
             ctx->nodes = ctx->leaves = nullptr;
             return ASR_HIP_OK;
         }
-        if (host[9]) {  // the root closes the list
+        if (host[F_ROOT]) {  // the root closes the list
             const u64 one = 1;
-            ASR_HIP_CHECK(ctx, hipMemcpyAsync(list + host[0], &one, sizeof(u64), hipMemcpyHostToDevice,
+            ASR_HIP_CHECK(ctx, hipMemcpyAsync(list + host[F_ENTRIES], &one, sizeof(u64), hipMemcpyHostToDevice,
                                               ctx->stream));
         }
         ctx->nodes = arena_alloc<u64>(ctx->persist, num_nodes);
@@ -2458,7 +2448,7 @@ int asr_geom_octree_build(asr_hip_context* ctx, const asr_octree_frame* frame, c
         i64* d_num = arena_alloc<i64>(ctx->scratch, 1);
         if (!ctx->nodes || !leaves_tmp || !lflag || !d_num) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
         // (every node key is a prefix of an inserted key or a sibling / face neighbour of one: never longer)
-        ASR_TRY(sort_keys(ctx, ctx->scratch, list, ctx->nodes, num_nodes, host[13] > 0 && host[13] <= 64 ? host[13] : 64));
+        ASR_TRY(sort_keys(ctx, ctx->scratch, list, ctx->nodes, num_nodes, host[F_KEY_BITS] > 0 && host[F_KEY_BITS] <= 64 ? host[F_KEY_BITS] : 64));
         k_leaf_flags<<<grid_for(num_nodes, BLK), BLK, 0, ctx->stream>>>(t, ctx->nodes, num_nodes, lflag);
         ASR_CHECK_LAUNCH(ctx);
         {
@@ -2519,9 +2509,9 @@ static int nb_key_maps(asr_hip_context* ctx, NbBatch& b, Pass&& pass, int grow0 
         k_map_build_batch<<<grid_for(b.base[b.n], BLK), BLK, 0, ctx->stream>>>(b, ctx->d_flags);
         ASR_CHECK_LAUNCH(ctx);
         ASR_TRY(pass());
-        int host[16];
+        HostFlags host;
         ASR_TRY(read_flags(ctx, host));
-        if (!host[1]) {
+        if (!host[F_OVERFLOW]) {
             if (grow_out) *grow_out = grow;
             return ASR_HIP_OK;
         }
@@ -2548,12 +2538,12 @@ static NbBatch nb_one_grid(const u64* keys, i64 v) {
 
 static int check_row_list(asr_hip_context* ctx, const int32_t* rows, i64 nrows, i64 v, int32_t* mark = nullptr) {
     ASR_TRY(ensure_flags(ctx));
-    ASR_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags + 3, 0, sizeof(int), ctx->stream));
+    ASR_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags + F_BAD_KEY, 0, sizeof(int), ctx->stream));
     k_check_rows<<<grid_for(nrows, BLK), BLK, 0, ctx->stream>>>(rows, nrows, v, ctx->d_flags, mark);
     ASR_CHECK_LAUNCH(ctx);
-    int host[16];
+    HostFlags host;
     ASR_TRY(read_flags(ctx, host));
-    if (host[3]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "neighbour rows: the row list must be strictly ascending indices in [0, %lld)", (long long)v);
+    if (host[F_BAD_KEY]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "neighbour rows: the row list must be strictly ascending indices in [0, %lld)", (long long)v);
     return ASR_HIP_OK;
 }
 
@@ -2738,41 +2728,60 @@ int asr_geom_row_groups_batch(asr_hip_context* ctx, const asr_row_group_job* job
     if (!wide_jobs.empty()) ASR_TRY(rg_batch_run(ctx, wide_jobs.data(), (int)wide_jobs.size(), seg, 54));
     return ASR_HIP_OK;
 }
-// *done = false: more than RG_MAX_MASKS distinct masks (or a full mask set): nothing written, the caller sorts on full masks
-static int rg_batch_run_ranked(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, i64 seg, bool* done) {
-    *done = false;
-    ASR_TRY(ensure_flags(ctx));
-    RowGroupBatch b;
+// the jobs that have rows, each padded to a multiple of 128 rows, in one index space; *total = its size (0: nothing to do)
+static int rg_pack(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, RowGroupBatch& b, i64* total) {
     b.n = 0;
-    i64 total = 0;
+    *total = 0;
     for (int j = 0; j < n; ++j) {
         if (jobs[j].v <= 0) continue;
-        b.base[b.n] = total;
+        b.base[b.n] = *total;
         b.v[b.n] = jobs[j].v;
         b.kidx[b.n] = jobs[j].kidx;
         b.rs[b.n] = jobs[j].rs;
         b.out[b.n] = jobs[j].perm_out;
-        total += (jobs[j].v + 127) / 128 * 128;
+        *total += (jobs[j].v + 127) / 128 * 128;
         ++b.n;
     }
-    if (b.n == 0) {
-        *done = true;
-        return ASR_HIP_OK;
-    }
-    b.base[b.n] = total;
-    if (total >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "row_groups: too many rows");
-    u64* masks = arena_alloc<u64>(ctx->scratch, total);
-    unsigned* keys = arena_alloc<unsigned>(ctx->scratch, total);
-    unsigned* keys_s = arena_alloc<unsigned>(ctx->scratch, total);
-    int32_t* ids = arena_alloc<int32_t>(ctx->scratch, total);
-    int32_t* ids_s = arena_alloc<int32_t>(ctx->scratch, total);
+    b.base[b.n] = *total;
+    if (*total >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "row_groups: too many rows");
+    return ASR_HIP_OK;
+}
+// what both key types end with: ids_s = the rows in (job, segment, mask) order, masks = slot mask per row.  Option row_lpt:
+// the 128-row chunks of every segment longest first (k_rg_chunk_keys); then each job's permutation is written.
+static int rg_finish(asr_hip_context* ctx, const RowGroupBatch& b, i64 total, i64 seg, const int32_t* ids_s, const u64* masks) {
     const i64 nc = total / 128;
     int32_t* ckey = arena_alloc<int32_t>(ctx->scratch, nc);
     int32_t* ckey_s = arena_alloc<int32_t>(ctx->scratch, nc);
     int32_t* cid = arena_alloc<int32_t>(ctx->scratch, nc);
     int32_t* cid_s = arena_alloc<int32_t>(ctx->scratch, nc);
-    if (!masks || !keys || !keys_s || !ids || !ids_s || !ckey || !ckey_s || !cid || !cid_s)
-        ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    if (!ckey || !ckey_s || !cid || !cid_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    const int lpt = ctx->opt.row_lpt != 0;
+    if (lpt) {
+        k_rg_chunk_keys<<<grid_for(nc * 64, BLK), BLK, 0, ctx->stream>>>(b, seg, ids_s, masks, ckey, cid);
+        ASR_CHECK_LAUNCH(ctx);
+        ASR_TRY((sort_pairs<int32_t, int32_t>(ctx, ctx->scratch, ckey, ckey_s, cid, cid_s, nc, 17)));
+    }
+    k_rg_apply<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, ids_s, cid_s, lpt);
+    ASR_CHECK_LAUNCH(ctx);
+    return ASR_HIP_OK;
+}
+// *done = false: more than RG_MAX_MASKS distinct masks (or a full mask set): nothing written, the caller sorts on full masks
+static int rg_batch_run_ranked(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, i64 seg, bool* done) {
+    *done = false;
+    ASR_TRY(ensure_flags(ctx));
+    RowGroupBatch b;
+    i64 total;
+    ASR_TRY(rg_pack(ctx, jobs, n, b, &total));
+    if (b.n == 0) {
+        *done = true;
+        return ASR_HIP_OK;
+    }
+    u64* masks = arena_alloc<u64>(ctx->scratch, total);
+    unsigned* keys = arena_alloc<unsigned>(ctx->scratch, total);
+    unsigned* keys_s = arena_alloc<unsigned>(ctx->scratch, total);
+    int32_t* ids = arena_alloc<int32_t>(ctx->scratch, total);
+    int32_t* ids_s = arena_alloc<int32_t>(ctx->scratch, total);
+    if (!masks || !keys || !keys_s || !ids || !ids_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
     HashTab t;
     ASR_TRY(make_table(ctx, ctx->scratch, RG_MASK_TAB, true, t));
     ASR_TRY(fresh_flags(ctx));
@@ -2785,65 +2794,32 @@ static int rg_batch_run_ranked(asr_hip_context* ctx, const asr_row_group_job* jo
     ASR_CHECK_LAUNCH(ctx);
     k_rg_mask_ranks<<<RG_MAX_MASKS / 256, 256, 0, ctx->stream>>>(t, mlist, mslot, ctx->d_flags);
     ASR_CHECK_LAUNCH(ctx);
-    int host[16];
+    HostFlags host;
     ASR_TRY(read_flags(ctx, host));
-    if (host[1] || host[2] > RG_MAX_MASKS) return ASR_HIP_OK;  // too many distinct masks for the ranked keys
-    const int rank_bits = bits_for(std::max(host[2], 2));
+    if (host[F_OVERFLOW] || host[F_MASKS] > RG_MAX_MASKS) return ASR_HIP_OK;  // too many distinct masks for the ranked keys
+    const int rank_bits = bits_for(std::max(host[F_MASKS], 2));
     k_rg_keys_ranked<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, seg, masks, t, keys, ids, rank_bits);
     ASR_CHECK_LAUNCH(ctx);
     ASR_TRY((sort_pairs<unsigned, int32_t>(ctx, ctx->scratch, keys, keys_s, ids, ids_s, total, 4 + 6 + rank_bits)));
-    const int lpt = ctx->opt.row_lpt != 0;
-    if (lpt) {
-        k_rg_chunk_keys<<<grid_for(nc * 64, BLK), BLK, 0, ctx->stream>>>(b, seg, ids_s, masks, ckey, cid);
-        ASR_CHECK_LAUNCH(ctx);
-        ASR_TRY((sort_pairs<int32_t, int32_t>(ctx, ctx->scratch, ckey, ckey_s, cid, cid_s, nc, 17)));
-    }
-    k_rg_apply<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, ids_s, cid_s, lpt);
-    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(rg_finish(ctx, b, total, seg, ids_s, masks));
     *done = true;
     return ASR_HIP_OK;
 }
 static int rg_batch_run(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, i64 seg, int mask_bits) {
     RowGroupBatch b;
-    b.n = 0;
-    i64 total = 0;
-    for (int j = 0; j < n; ++j) {
-        if (jobs[j].v <= 0) continue;
-        b.base[b.n] = total;
-        b.v[b.n] = jobs[j].v;
-        b.kidx[b.n] = jobs[j].kidx;
-        b.rs[b.n] = jobs[j].rs;
-        b.out[b.n] = jobs[j].perm_out;
-        total += (jobs[j].v + 127) / 128 * 128;
-        ++b.n;
-    }
+    i64 total;
+    ASR_TRY(rg_pack(ctx, jobs, n, b, &total));
     if (b.n == 0) return ASR_HIP_OK;
-    b.base[b.n] = total;
-    if (total >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "row_groups: too many rows");
     u64* keys = arena_alloc<u64>(ctx->scratch, total);
     u64* keys_s = arena_alloc<u64>(ctx->scratch, total);
     u64* masks = arena_alloc<u64>(ctx->scratch, total);
     int32_t* ids = arena_alloc<int32_t>(ctx->scratch, total);
     int32_t* ids_s = arena_alloc<int32_t>(ctx->scratch, total);
-    const i64 nc = total / 128;
-    int32_t* ckey = arena_alloc<int32_t>(ctx->scratch, nc);
-    int32_t* ckey_s = arena_alloc<int32_t>(ctx->scratch, nc);
-    int32_t* cid = arena_alloc<int32_t>(ctx->scratch, nc);
-    int32_t* cid_s = arena_alloc<int32_t>(ctx->scratch, nc);
-    if (!keys || !keys_s || !masks || !ids || !ids_s || !ckey || !ckey_s || !cid || !cid_s)
-        ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    if (!keys || !keys_s || !masks || !ids || !ids_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
     k_rg_keys<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, seg, keys, masks, ids, mask_bits);
     ASR_CHECK_LAUNCH(ctx);
     ASR_TRY((sort_pairs<u64, int32_t>(ctx, ctx->scratch, keys, keys_s, ids, ids_s, total, 4 + 6 + mask_bits)));
-    const int lpt = ctx->opt.row_lpt != 0;
-    if (lpt) {
-        k_rg_chunk_keys<<<grid_for(nc * 64, BLK), BLK, 0, ctx->stream>>>(b, seg, ids_s, masks, ckey, cid);
-        ASR_CHECK_LAUNCH(ctx);
-        ASR_TRY((sort_pairs<int32_t, int32_t>(ctx, ctx->scratch, ckey, ckey_s, cid, cid_s, nc, 17)));
-    }
-    k_rg_apply<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, ids_s, cid_s, lpt);
-    ASR_CHECK_LAUNCH(ctx);
-    return ASR_HIP_OK;
+    return rg_finish(ctx, b, total, seg, ids_s, masks);
 }
 
 // CombineSiblings in two steps (k_coarsen_flags above); the keys are sorted and unique, as those of every grid.
@@ -3034,10 +3010,10 @@ static int build_point_index(asr_hip_context* ctx, const asr_octree_frame* frame
 }
 static int build_cell_table(asr_hip_context* ctx, i64 n, int lmin, int lmax, RadiusState& st, bool hash_all, Arena* where) {
     Arena& arena = where ? *where : ctx->scratch;
-    int host[16];
+    HostFlags host;
     const u64* codes = st.codes;
     HashTab dummy{nullptr, nullptr, 0};
-    int* level_cnt = ctx->d_flags + 32;  // cells per level
+    int* level_cnt = ctx->d_flags + FLAG_LEVEL_CELLS;  // cells per level
     int host_lvl[ASR_MAX_LEVEL + 1] = {0};
     if (n > 0) {
         ASR_HIP_CHECK(ctx, hipMemsetAsync(level_cnt, 0, (ASR_MAX_LEVEL + 1) * sizeof(int), ctx->stream));
@@ -3047,7 +3023,7 @@ static int build_cell_table(asr_hip_context* ctx, i64 n, int lmin, int lmax, Rad
         ASR_HIP_CHECK(ctx, hipMemcpyAsync(host_lvl, level_cnt, sizeof(host_lvl), hipMemcpyDeviceToHost, ctx->stream));
     }
     ASR_TRY(read_flags(ctx, host));
-    if (host[11]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "points contain non-finite values");
+    if (host[F_NONFINITE]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "points contain non-finite values");
     // Levels whose cells hold fewer than two points on average stay out of the hash table (a cloud with very dense
     // spots has query levels at which every point is a cell: 10^7 insertions per level); they are served by binary
     // search (cell_range).  Option search_hash_level forces the finest hashed level (tests).
@@ -3073,6 +3049,28 @@ static int build_cell_table(asr_hip_context* ctx, i64 n, int lmin, int lmax, Rad
         ASR_CHECK_LAUNCH(ctx);
     }
     return ASR_HIP_OK;
+}
+// build_point_index that returns only with a table that lost no key: one that overflowed (lattice-like clouds crowd a few
+// buckets, see TabProbe) is built again four times the size, in the same scratch.  The growth starts at the context's and is
+// kept there, so that the next index of any entry point starts where this one ended.  The flag is read before any kernel
+// walks the table: one that lost keys misses neighbours.  `what`: the failure message.
+static int build_point_index_grown(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, int lmin,
+                                   int lmax, RadiusState& st, const char* what, Arena* keep = nullptr, bool want_rank = false,
+                                   bool hash_all = true, const float* radii = nullptr) {
+    st.cell_grow = rstate(ctx).cell_grow;
+    HostFlags host;
+    ArenaMark mark;
+    arena_mark(ctx->scratch, mark);
+    for (;;) {
+        ASR_TRY(build_point_index(ctx, frame, pts, n, lmin, lmax, st, keep, want_rank, hash_all, radii));
+        ASR_TRY(read_flags(ctx, host));
+        if (!host[F_OVERFLOW]) return ASR_HIP_OK;
+        if (st.cell_grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "%s", what);
+        st.cell_grow += 2;
+        rstate(ctx).cell_grow = st.cell_grow;
+        ++ctx->table_regrows;
+        arena_rewind(ctx->scratch, mark);
+    }
 }
 
 constexpr int PRESORT_LEVEL = 13;  // the least depth of the early sort (five 8-bit passes either way)
@@ -3101,13 +3099,13 @@ int asr_geom_presort(asr_hip_context* ctx, Arena& keep, const asr_octree_frame* 
     if (n <= 0 || n >= (i64(1) << 31)) return ASR_HIP_OK;
     int lsort = PRESORT_LEVEL;
     if (radius_scale > 0.f && radii) {
-        int host[16];
+        HostFlags host;
         ASR_TRY(fresh_flags(ctx));
         k_finest_point_level<<<std::min<unsigned>(grid_for(n, BLK), 2048u), BLK, 0, ctx->stream>>>(
-                *frame, radii, n, radius_scale, std::min(max_depth, ASR_MAX_LEVEL), ctx->d_flags + 8);
+                *frame, radii, n, radius_scale, std::min(max_depth, ASR_MAX_LEVEL), ctx->d_flags + F_POINT_LEVEL);
         ASR_CHECK_LAUNCH(ctx);
         ASR_TRY(read_flags(ctx, host));
-        lsort = std::max(PRESORT_LEVEL, std::min(ASR_MAX_LEVEL, host[8] + 1));
+        lsort = std::max(PRESORT_LEVEL, std::min(ASR_MAX_LEVEL, host[F_POINT_LEVEL] + 1));
     }
     RadiusState st;
     ASR_TRY(sort_points(ctx, frame, pts, n, lsort, st, &keep, true, radii, true));
@@ -3137,9 +3135,9 @@ int asr_geom_precells(asr_hip_context* ctx, Arena& keep) {
     st.cell_grow = rstate(ctx).cell_grow;
     ASR_TRY(fresh_flags(ctx));
     ASR_TRY(build_cell_table(ctx, pi.n, 1, pi.lsort, st, false, &keep));
-    int host[16];
+    HostFlags host;
     ASR_TRY(read_flags(ctx, host));
-    if (host[1]) {  // overflow: the query builds (and grows) its own table
+    if (host[F_OVERFLOW]) {  // overflow: the query builds (and grows) its own table
         ++ctx->table_regrows;
         return ASR_HIP_OK;
     }
@@ -3154,18 +3152,24 @@ int asr_geom_precells(asr_hip_context* ctx, Arena& keep) {
     return ASR_HIP_OK;
 }
 
+// widen > 0: the range from the finest level a row starts on to the coarsest it reaches with its size times `widen`, over
+// the rows that search at all (k_attr_levels); *lmin > *lmax when there is none
 static int query_level_range(asr_hip_context* ctx, const asr_octree_frame* frame, const float* sizes,
-                             i64 v, int* lmin, int* lmax) {
-    int host[16];
+                             i64 v, int* lmin, int* lmax, float widen = 0.f) {
+    HostFlags host;
     ASR_TRY(fresh_flags(ctx));
-    int init[2] = {ASR_MAX_LEVEL, 0};
-    ASR_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_flags + 6, init, 2 * sizeof(int),
+    const int init[2] = {ASR_MAX_LEVEL, 0};  // F_LEVEL_MIN, F_LEVEL_MAX
+    ASR_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_flags + F_LEVEL_MIN, init, 2 * sizeof(int),
                                       hipMemcpyHostToDevice, ctx->stream));
-    k_query_levels<<<std::min<unsigned>(grid_for(v, BLK), 2048u), BLK, 0, ctx->stream>>>(*frame, sizes, v, ctx->d_flags);
+    const unsigned grid = std::min<unsigned>(grid_for(v, BLK), 2048u);
+    if (widen > 0.f)
+        k_attr_levels<<<grid, BLK, 0, ctx->stream>>>(*frame, sizes, v, widen, ctx->d_flags);
+    else
+        k_query_levels<<<grid, BLK, 0, ctx->stream>>>(*frame, sizes, v, ctx->d_flags);
     ASR_CHECK_LAUNCH(ctx);
     ASR_TRY(read_flags(ctx, host));
-    *lmin = host[6];
-    *lmax = host[7];
+    *lmin = host[F_LEVEL_MIN];
+    *lmax = host[F_LEVEL_MAX];
     return ASR_HIP_OK;
 }
 
@@ -3182,7 +3186,7 @@ int asr_geom_radius_count(asr_hip_context* ctx, const asr_octree_frame* frame, c
         return ASR_HIP_OK;
     }
     if (n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "too many points for int32 indices");
-    int host[16];
+    HostFlags host;
     st.v = v;
     int lmin = lmin_hint, lmax = lmax_hint;
     if (lmin < 0 || lmax < lmin) ASR_TRY(query_level_range(ctx, frame, sizes, v, &lmin, &lmax));
@@ -3240,34 +3244,34 @@ int asr_geom_radius_count(asr_hip_context* ctx, const asr_octree_frame* frame, c
     st.is_heavy = arena_alloc<uint8_t>(ctx->scratch, v);
     int2* extras = arena_alloc<int2>(ctx->scratch, EXTRA_CAP);
     if (!counts || !st.tmp || !st.heavy || !st.is_heavy || !extras) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-    ASR_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags + 10, 0, sizeof(int), ctx->stream));
-    ASR_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags + 15, 0, sizeof(int), ctx->stream));
-    st.aq = AlignedQ{voxel_keys, extras, ctx->d_flags + 15, lhalf_max};
+    ASR_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags + F_HEAVY, 0, sizeof(int), ctx->stream));
+    ASR_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags + F_MARGIN_PAIRS, 0, sizeof(int), ctx->stream));
+    st.aq = AlignedQ{voxel_keys, extras, ctx->d_flags + F_MARGIN_PAIRS, lhalf_max};
     // one pass: counts, the sorted light rows (fixed slots) and the list of heavy rows
     if (st.aligned && ep.lmax >= ep.lmin && n > 0) {
         k_radius_extras<<<grid_for(n, BLK), BLK, 0, ctx->stream>>>(st.codes, st.sorted, n, voxel_keys, v, centers, sizes,
-                                                                  ep, extras, ctx->d_flags + 15);
+                                                                  ep, extras, ctx->d_flags + F_MARGIN_PAIRS);
         ASR_CHECK_LAUNCH(ctx);
     }
     const unsigned qgrid = grid_for(v + 1, 4);
     if (st.aligned_main)
         k_radius_query<2, true><<<qgrid, BLK, 0, ctx->stream>>>(*frame, st.sorted, centers, sizes, v, st.index(), st.aq, counts,
-                                                                st.tmp, st.heavy, ctx->d_flags + 10, st.is_heavy);
+                                                                st.tmp, st.heavy, ctx->d_flags + F_HEAVY, st.is_heavy);
     else
         k_radius_query<2, false><<<qgrid, BLK, 0, ctx->stream>>>(*frame, st.sorted, centers, sizes, v, st.index(), st.aq, counts,
-                                                                 st.tmp, st.heavy, ctx->d_flags + 10, st.is_heavy);
+                                                                 st.tmp, st.heavy, ctx->d_flags + F_HEAVY, st.is_heavy);
     ASR_CHECK_LAUNCH(ctx);
     ASR_TRY(read_flags(ctx, host));
-    if (host[1]) {  // retry with a table four times the size
+    if (host[F_OVERFLOW]) {  // retry with a table four times the size
         if (st.cell_grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "radius search cell table overflow");
         st.cell_grow += 2;
         ++ctx->table_regrows;
         return asr_geom_radius_count(ctx, frame, pts, n, centers, sizes, v, rs, num_pairs, keep, radii, voxel_keys,
                                      lmin_hint, lmax_hint, pre);
     }
-    if (host[15] > EXTRA_CAP) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "radius search: %d pairs in the rounding margin (cap %d)", host[15], EXTRA_CAP);
-    ctx->search_extras = host[15];
-    st.num_heavy = host[10];
+    if (host[F_MARGIN_PAIRS] > EXTRA_CAP) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "radius search: %d pairs in the rounding margin (cap %d)", host[F_MARGIN_PAIRS], EXTRA_CAP);
+    ctx->search_extras = host[F_MARGIN_PAIRS];
+    st.num_heavy = host[F_HEAVY];
     if (st.num_heavy > 0) {
         st.hc_pref = arena_alloc<int>(ctx->scratch, (size_t)st.num_heavy * HC_LD);
         st.hc_beg = arena_alloc<int>(ctx->scratch, (size_t)st.num_heavy * HC_LD);
@@ -3302,21 +3306,9 @@ int asr_geom_radius_neighbor_count(asr_hip_context* ctx, const asr_octree_frame*
     if (n <= 0) return ASR_HIP_OK;
     if (n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "too many points for int32 indices");
     RadiusState st;
-    st.cell_grow = rstate(ctx).cell_grow;
-    int host[16], lmin, lmax;
+    int lmin, lmax;
     ASR_TRY(query_level_range(ctx, frame, radii, n, &lmin, &lmax));
-    ArenaMark mark;
-    arena_mark(ctx->scratch, mark);
-    for (;;) {
-        ASR_TRY(build_point_index(ctx, frame, pts, n, lmin, lmax, st, nullptr, false, false));
-        ASR_TRY(read_flags(ctx, host));
-        if (!host[1]) break;
-        if (st.cell_grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "cell table overflow");
-        st.cell_grow += 2;  // lattice-like clouds crowd a few buckets (see TabProbe): a table four times the size
-        rstate(ctx).cell_grow = st.cell_grow;
-        ++ctx->table_regrows;
-        arena_rewind(ctx->scratch, mark);
-    }
+    ASR_TRY(build_point_index_grown(ctx, frame, pts, n, lmin, lmax, st, "cell table overflow", nullptr, false, false));
     i64* counts = arena_alloc<i64>(ctx->scratch, n + 1);
     if (!counts) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
     k_radius_query<0, false><<<grid_for(n + 1, 4), BLK, 0, ctx->stream>>>(
@@ -3337,31 +3329,13 @@ int asr_geom_attributes_at(asr_hip_context* ctx, const asr_octree_frame* frame, 
     ASR_TRY(ensure_flags(ctx));
     if (m <= 0) return ASR_HIP_OK;
     if (n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "too many points for int32 indices");
-    int host[16];
-    ASR_TRY(fresh_flags(ctx));
-    const int init[2] = {ASR_MAX_LEVEL, 0};
-    ASR_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_flags + 6, init, 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    k_attr_levels<<<std::min<unsigned>(grid_for(m, BLK), 2048u), BLK, 0, ctx->stream>>>(*frame, sizes, m,
-                                                                                       std::ldexp(1.f, max_widen), ctx->d_flags);
-    ASR_CHECK_LAUNCH(ctx);
-    ASR_TRY(read_flags(ctx, host));
-    int lmin = host[6], lmax = host[7];
+    int lmin, lmax;
+    ASR_TRY(query_level_range(ctx, frame, sizes, m, &lmin, &lmax, std::ldexp(1.f, max_widen)));
     if (lmin > lmax) lmin = lmax = 0;  // no searchable row at all
     const int cp = c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : c <= 8 ? 8 : 16;
     RadiusState st;
-    st.cell_grow = rstate(ctx).cell_grow;
-    ArenaMark mark;
-    arena_mark(ctx->scratch, mark);
-    for (;;) {
-        ASR_TRY(build_point_index(ctx, frame, pts, n, lmin, lmax, st, nullptr, false, false, radii));
-        ASR_TRY(read_flags(ctx, host));
-        if (!host[1]) break;
-        if (st.cell_grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "radius search cell table overflow");
-        st.cell_grow += 2;  // lattice-like clouds crowd a few buckets (see TabProbe): a table four times the size
-        rstate(ctx).cell_grow = st.cell_grow;
-        ++ctx->table_regrows;
-        arena_rewind(ctx->scratch, mark);
-    }
+    ASR_TRY(build_point_index_grown(ctx, frame, pts, n, lmin, lmax, st, "radius search cell table overflow", nullptr, false,
+                                    false, radii));
     float* sattr = arena_alloc<float>(ctx->scratch, (size_t)(n + 1) * cp);
     if (!sattr) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
 #define ASR_ATTR_BLEND(CP_)                                                                                                  \
@@ -3393,6 +3367,29 @@ static int deepen_point_index(asr_hip_context* ctx, const float* pts, RadiusStat
     ASR_CHECK_LAUNCH(ctx);
     return ASR_HIP_OK;
 }
+// finest level of the kNN / nearest-point index: about one point per cell if the cloud filled the cube
+static int knn_fine_level(i64 n) {
+    int lfine = 1;
+    while (lfine < ASR_MAX_LEVEL - 1 && (i64(1) << (3 * lfine)) < n) ++lfine;
+    return lfine;
+}
+// Dense spots: a finest-level cell with thousands of points makes every one of them walk thousands of candidates.  Such
+// clouds get their points sorted eight levels deeper (option knn_deep), and the points of crowded cells start on a finer
+// level.  *ldeep = the level the points are sorted down to.  One read-back (the largest cell population).
+static int deepen_crowded_index(asr_hip_context* ctx, const float* pts, RadiusState& st, int lfine, int* ldeep) {
+    HostFlags host;
+    *ldeep = lfine;
+    ASR_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags + F_MAX_CELL_POP, 0, sizeof(int), ctx->stream));
+    k_max_cell_pop<<<grid_for((i64)st.tab.mask + 1, BLK), BLK, 0, ctx->stream>>>(st.tab, st.start, st.end, lfine,
+                                                                               ctx->d_flags + F_MAX_CELL_POP);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY(read_flags(ctx, host));
+    if (host[F_MAX_CELL_POP] > KNN_CROWD && ctx->opt.knn_deep) {
+        *ldeep = std::min<int>(ASR_MAX_LEVEL, lfine + 8);
+        ASR_TRY(deepen_point_index(ctx, pts, st, *ldeep));
+    }
+    return ASR_HIP_OK;
+}
 
 // KDTree::ComputeKRadius / ComputeInlier (cpp/lib/nsearch.cpp:30-86)
 int asr_geom_knn(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, int k,
@@ -3402,54 +3399,28 @@ int asr_geom_knn(asr_hip_context* ctx, const asr_octree_frame* frame, const floa
     if (n <= 0) return ASR_HIP_OK;
     if (k < 1) ASR_FAIL(ctx, ASR_HIP_EINVAL, "knn: k must be >= 1");
     if (n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "too many points for int32 indices");
-    // finest level: about one point per cell if the cloud filled the cube
-    int lfine = 1;
-    while (lfine < ASR_MAX_LEVEL - 1 && (i64(1) << (3 * lfine)) < n) ++lfine;
+    const int lfine = knn_fine_level(n);
     RadiusState st;
-    st.cell_grow = rstate(ctx).cell_grow;
-    int host[16];
-    ArenaMark mark;
-    arena_mark(ctx->scratch, mark);
-    for (;;) {  // the overflow is read before any kernel walks the table: one that lost keys misses neighbours
-        ASR_TRY(build_point_index(ctx, frame, pts, n, 0, lfine, st));
-        ASR_TRY(read_flags(ctx, host));
-        if (!host[1]) break;
-        if (st.cell_grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "cell table overflow");
-        st.cell_grow += 2;  // lattice-like clouds crowd a few buckets (see TabProbe): a table four times the size
-        rstate(ctx).cell_grow = st.cell_grow;
-        ++ctx->table_regrows;
-        arena_rewind(ctx->scratch, mark);
-    }
+    HostFlags host;
+    ASR_TRY(build_point_index_grown(ctx, frame, pts, n, 0, lfine, st, "cell table overflow"));
     st.lhash = lfine;
-    // dense spots: a finest-level cell with thousands of points makes every one of them walk thousands of candidates.
-    // Such clouds get their points sorted eight levels deeper, and the points of crowded cells start on a finer level.
-    int ldeep = lfine;
-    {
-        ASR_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags + 14, 0, sizeof(int), ctx->stream));
-        k_max_cell_pop<<<grid_for((i64)st.tab.mask + 1, BLK), BLK, 0, ctx->stream>>>(st.tab, st.start, st.end, lfine,
-                                                                                   ctx->d_flags + 14);
-        ASR_CHECK_LAUNCH(ctx);
-        ASR_TRY(read_flags(ctx, host));
-        if (host[14] > KNN_CROWD && ctx->opt.knn_deep) {
-            ldeep = std::min<int>(ASR_MAX_LEVEL, lfine + 8);
-            ASR_TRY(deepen_point_index(ctx, pts, st, ldeep));
-        }
-    }
+    int ldeep;
+    ASR_TRY(deepen_crowded_index(ctx, pts, st, lfine, &ldeep));
     const bool fast = !inlier_out && radii_out && k <= 32 && n >= k && ctx->opt.knn_cells;
     if (fast) {
         // cell-parallel pass, then the wave-per-point kernel for what it could not certify
         int32_t* cells = arena_alloc<int32_t>(ctx->scratch, n + 1);
         int32_t* fallback = arena_alloc<int32_t>(ctx->scratch, n + 1);
         if (!cells || !fallback) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-        ASR_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags + 12, 0, 2 * sizeof(int), ctx->stream));
-        k_cell_list<<<grid_for(n, 4096), BLK, 0, ctx->stream>>>(st.codes, n, lfine, cells, ctx->d_flags + 12);
+        ASR_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags + F_KNN_CELLS, 0, 2 * sizeof(int), ctx->stream));  // + F_KNN_FALLBACK
+        k_cell_list<<<grid_for(n, 4096), BLK, 0, ctx->stream>>>(st.codes, n, lfine, cells, ctx->d_flags + F_KNN_CELLS);
         ASR_CHECK_LAUNCH(ctx);
         ASR_TRY(read_flags(ctx, host));
-        const i64 ncells = host[12];
+        const i64 ncells = host[F_KNN_CELLS];
 #define ASR_KNN_CELLS(K_)                                                                                           \
     k_knn_cells<K_><<<grid_for(ncells, 4), BLK, 0, ctx->stream>>>(*frame, st.sorted, n, st.tab, st.start, st.end, lfine, \
                                                                    k, cells, ncells, radii_out, fallback,            \
-                                                                   ctx->d_flags + 13)
+                                                                   ctx->d_flags + F_KNN_FALLBACK)
         if (k <= 8)
             ASR_KNN_CELLS(8);
         else if (k <= 16)
@@ -3461,7 +3432,7 @@ int asr_geom_knn(asr_hip_context* ctx, const asr_octree_frame* frame, const floa
 #undef ASR_KNN_CELLS
         ASR_CHECK_LAUNCH(ctx);
         ASR_TRY(read_flags(ctx, host));
-        const i64 nfb = host[13];
+        const i64 nfb = host[F_KNN_FALLBACK];
         if (nfb > 0) {
             k_knn<<<grid_for(nfb, 4), BLK, 0, ctx->stream>>>(*frame, st.sorted, n, st.index(), lfine, ldeep, k, radii_in,
                                                              radius_fraction, outlier_threshold, radii_out, nullptr,
@@ -3484,34 +3455,12 @@ int asr_geom_nearest(asr_hip_context* ctx, const asr_octree_frame* frame, const 
                      i64 m, int32_t* index_out, float* sqdist_out) {
     ASR_TRY(ensure_flags(ctx));
     if (m <= 0 || (!index_out && !sqdist_out)) return ASR_HIP_OK;
-    int lfine = 1;
-    while (lfine < ASR_MAX_LEVEL - 1 && (i64(1) << (3 * lfine)) < n) ++lfine;
+    const int lfine = knn_fine_level(n);
     RadiusState st;
-    st.cell_grow = rstate(ctx).cell_grow;
-    int host[16];
-    ArenaMark mark;
-    arena_mark(ctx->scratch, mark);
-    for (;;) {
-        ASR_TRY(build_point_index(ctx, frame, pts, n, 0, lfine, st));
-        ASR_TRY(read_flags(ctx, host));
-        if (!host[1]) break;
-        if (st.cell_grow >= 6) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "nearest point: cell table overflow");
-        st.cell_grow += 2;  // lattice-like clouds crowd a few buckets (see TabProbe): a table four times the size
-        rstate(ctx).cell_grow = st.cell_grow;
-        ++ctx->table_regrows;
-        arena_rewind(ctx->scratch, mark);
-    }
+    ASR_TRY(build_point_index_grown(ctx, frame, pts, n, 0, lfine, st, "nearest point: cell table overflow"));
     st.lhash = lfine;
-    int ldeep = lfine;
-    ASR_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags + 14, 0, sizeof(int), ctx->stream));
-    k_max_cell_pop<<<grid_for((i64)st.tab.mask + 1, BLK), BLK, 0, ctx->stream>>>(st.tab, st.start, st.end, lfine,
-                                                                               ctx->d_flags + 14);
-    ASR_CHECK_LAUNCH(ctx);
-    ASR_TRY(read_flags(ctx, host));
-    if (host[14] > KNN_CROWD && ctx->opt.knn_deep) {
-        ldeep = std::min<int>(ASR_MAX_LEVEL, lfine + 8);
-        ASR_TRY(deepen_point_index(ctx, pts, st, ldeep));
-    }
+    int ldeep;
+    ASR_TRY(deepen_crowded_index(ctx, pts, st, lfine, &ldeep));
     u64* qcodes_u = arena_alloc<u64>(ctx->scratch, m);
     u64* qcodes = arena_alloc<u64>(ctx->scratch, m);
     int32_t* qids_u = arena_alloc<int32_t>(ctx->scratch, m);
@@ -3648,13 +3597,14 @@ int asr_geom_dual_fill(asr_hip_context* ctx, i64* out) {
     const i64 nl = st.dual_nl;
     if (nl <= 0) return ASR_HIP_OK;
     if (st.v != -nl) ASR_FAIL(ctx, ASR_HIP_EINVAL, "dual_fill must follow the matching dual_count call");
-    int host[16];
+    HostFlags host;
     k_dual_fill<<<grid_for(nl, BLK), BLK, 0, ctx->stream>>>(st.dual_leaves, nl, st.tab, (const i64*)st.start, out,
                                                             ctx->d_flags);
     ASR_CHECK_LAUNCH(ctx);
     ASR_TRY(read_flags(ctx, host));
     st.v = 0;
-    if (host[1]) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "invalid key after searching for node (cpp/lib/grid.cpp:435-440)");
+    // (F_OVERFLOW: the node map of the _count call lost a key -- the same block when nothing ran in between)
+    if (host[F_DUAL_KEY] || host[F_OVERFLOW]) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "invalid key after searching for node (cpp/lib/grid.cpp:435-440)");
     return ASR_HIP_OK;
 }
 

@@ -76,7 +76,7 @@ __device__ inline bool crossing(const float* values, float thr, i64 a, i64 b) { 
 }
 
 // one thread per dual cell: active flag and number of distinct corner voxels.  A cell with a corner outside
-// [0, nv) raises flags[4] and counts as inactive: no later kernel loads through its indices.
+// [0, nv) raises flags[F_BAD_INDEX] and counts as inactive: no later kernel loads through its indices.
 __global__ void k_contour_active(const float* values, i64 nv, const i64* duals, i64 nd, float thr, i64* flag,
                                  i64* npairs, int* flags) {
     i64 d = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -93,7 +93,7 @@ __global__ void k_contour_active(const float* values, i64 nv, const i64* duals, 
         in_range &= c[k] >= 0 && c[k] < nv;
     }
     if (!in_range) {
-        atomicOr(&flags[4], 1);
+        atomicOr(&flags[F_BAD_INDEX], 1);
         flag[d] = 0;
         npairs[d] = 0;
         return;
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(BLK) void k_contour_edges(const float* values, cons
     if (!FILL) {
         tri_cnt[t] = n == 3 ? 1 : (n == 4 ? 2 : (n > 4 ? n : 0));
         extra_cnt[t] = n > 4 ? 1 : 0;
-        if (n > ASR_USET_CAP) atomicOr(&flags[2], 1);
+        if (n > ASR_USET_CAP) atomicOr(&flags[F_DUAL_FAN], 1);
         return;
     }
     // n == 2 emits nothing but is sorted all the same: the reference sorts before it looks at n (:360-369), and two
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(BLK) void k_contour_edges(const float* values, cons
             sorted[ns - 1 - j] = s;
         }
     if (ns != n) {  // "this should not happen: cannot sort duals" (:366-370)
-        atomicOr(&flags[3], 1);
+        atomicOr(&flags[F_DUAL_SORT], 1);
         return;
     }
     if (n < 3) return;
@@ -386,7 +386,7 @@ __global__ void k_uf_link(const int32_t* tri, i64 nt, i64 nv, int* parent, int* 
     if (f >= nt) return;
     const int a = tri[f * 3], b = tri[f * 3 + 1], c = tri[f * 3 + 2];
     if (a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv) {
-        atomicOr(&flags[4], 1);
+        atomicOr(&flags[F_BAD_INDEX], 1);
         return;
     }
     uf_union(parent, a, b);
@@ -484,7 +484,7 @@ __global__ void k_tri_areas(const float* vtx, i64 nv, const int32_t* tri, i64 nt
     if (t >= nt) return;
     const int a = tri[t * 3], b = tri[t * 3 + 1], c = tri[t * 3 + 2];
     if (a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv) {
-        atomicOr(&flags[4], 1);
+        atomicOr(&flags[F_BAD_INDEX], 1);
         area[t] = 0.0;
         return;
     }
@@ -554,9 +554,9 @@ __global__ void k_simp_keys(asr_octree_frame f, const float* vtx, i64 nv, const 
     int x = 0, y = 0, z = 0;
     u64 key = 1;  // the root: what a refused vertex gets (the call fails before anything reads it)
     if (l < 0 || l > ASR_MAX_LEVEL) {
-        atomicOr(&flags[5], 1);
+        atomicOr(&flags[F_BAD_LEVEL], 1);
     } else if (!frame_coord21_checked(f, vtx[3 * i], vtx[3 * i + 1], vtx[3 * i + 2], x, y, z)) {
-        atomicOr(&flags[6], 1);
+        atomicOr(&flags[F_OUTSIDE], 1);
     } else {
         const int s = ASR_MAX_LEVEL - l;
         key = asr_coord_key(x >> s, y >> s, z >> s, l);
@@ -592,7 +592,7 @@ __global__ void k_simp_corner_keys(const int32_t* tri, i64 ncorner, i64 nv, cons
     const int v = tri[q];
     u32 c = 0;
     if (v < 0 || v >= nv)
-        atomicOr(&flags[4], 1);
+        atomicOr(&flags[F_BAD_INDEX], 1);
     else
         c = (u32)cluster[v];
     ck[q] = c;
@@ -778,7 +778,7 @@ __global__ void k_adj_edge_keys(const int32_t* tri, i64 nq, i64 nv, u64* keys, i
     u64 key = (u64)nv << 32;
     bool degen = false;
     if (c0 < 0 || c1 < 0 || c2 < 0 || c0 >= nv || c1 >= nv || c2 >= nv) {
-        if (j == 0) atomicOr(&flags[4], 1);
+        if (j == 0) atomicOr(&flags[F_BAD_INDEX], 1);
     } else if (c0 == c1 || c1 == c2 || c0 == c2) {
         degen = j == 0;
     } else {
@@ -902,7 +902,7 @@ __global__ void k_smooth_load(const float* vtx, i64 nv, double* pos, int* flags)
     const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nv) return;
     const float x = vtx[3 * i], y = vtx[3 * i + 1], z = vtx[3 * i + 2];
-    if (!(isfinite(x) && isfinite(y) && isfinite(z))) atomicOr(&flags[7], 1);
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) atomicOr(&flags[F_BAD_VERTEX], 1);
     pos_store(pos, i, (double)x, (double)y, (double)z);
 }
 __global__ void k_smooth_store(const double* pos, i64 nv, float* vtx) {
@@ -1064,7 +1064,7 @@ __global__ void k_fill_keys(const float* vtx, const int* root_of, const uint8_t*
     u64 key = (u64)nv << 32;
     if (r >= 0 && filled_rim[r]) {
         const float x = vtx[3 * i], y = vtx[3 * i + 1], z = vtx[3 * i + 2];
-        if (!(isfinite(x) && isfinite(y) && isfinite(z))) atomicOr(&flags[7], 1);
+        if (!(isfinite(x) && isfinite(y) && isfinite(z))) atomicOr(&flags[F_BAD_VERTEX], 1);
         key = ((u64)(u32)r << 32) | (u64)(u32)i;
     }
     keys[i] = key;
@@ -1190,9 +1190,9 @@ int asr_mesh_contour_count(asr_hip_context* ctx, const float* values, i64 num_va
     i64 na = 0, np = 0;
     ASR_TRY(read_i64(ctx, voff + num_duals, &na));
     ASR_TRY(read_i64(ctx, poff + num_duals, &np));
-    int host[16];
+    HostFlags host;
     ASR_TRY(read_flags(ctx, host));
-    if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "contour: dual vertex index out of range");
+    if (host[F_BAD_INDEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "contour: dual vertex index out of range");
     st.values = values;
     st.duals = duals;
     st.num_values = num_values;
@@ -1231,7 +1231,7 @@ int asr_mesh_contour_count(asr_hip_context* ctx, const float* values, i64 num_va
     ASR_TRY(read_i64(ctx, tri_off + na * 3, &st.num_tri));
     ASR_TRY(read_i64(ctx, extra_off + na * 3, &st.num_extra));
     ASR_TRY(read_flags(ctx, host));
-    if (host[2])
+    if (host[F_DUAL_FAN])
         ASR_FAIL(ctx, ASR_HIP_ELOGIC, "contour: more than %d dual cells around one edge", ASR_USET_CAP);
     if (na + st.num_extra >= (i64(1) << 31) || st.num_tri >= (i64(1) << 31) / 3)
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "contour: mesh does not fit 32-bit indices");
@@ -1259,9 +1259,9 @@ int asr_mesh_contour_fill(asr_hip_context* ctx, float* vertices, int32_t* triang
                                                                 st.adj_rs, st.adj, nullptr, nullptr, st.tri_off,
                                                                 st.extra_off, vertices, triangles, ctx->d_flags);
     ASR_CHECK_LAUNCH(ctx);
-    int host[16];
+    HostFlags host;
     ASR_TRY(read_flags(ctx, host));
-    if (host[3]) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "this should not happen: cannot sort duals (cpp/lib/contouring.cpp:366-370)");
+    if (host[F_DUAL_SORT]) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "this should not happen: cannot sort duals (cpp/lib/contouring.cpp:366-370)");
     return ASR_HIP_OK;
 }
 
@@ -1294,9 +1294,9 @@ int asr_mesh_components_count(asr_hip_context* ctx, const float* vertices, i64 n
     ASR_TRY(scan_counts(ctx, ctx->scratch, is_root, label, nv + 1));
     i64 nc = 0;
     ASR_TRY(read_i64(ctx, label + nv, &nc));
-    int host[16];
+    HostFlags host;
     ASR_TRY(read_flags(ctx, host));
-    if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "components: triangle index out of range");
+    if (host[F_BAD_INDEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "components: triangle index out of range");
     MESH_ALLOC(sizes, int, nc);
     MESH_ALLOC(keys, u64, nc);
     MESH_ALLOC(keys_sorted, u64, nc);
@@ -1404,13 +1404,13 @@ int asr_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* frame,
         ASR_CHECK_LAUNCH(ctx);
     }
     i64 nc = 0;
-    int host[16];
+    HostFlags host;
     ASR_TRY(read_i64(ctx, hoff + nv, &nc));
     ASR_TRY(read_flags(ctx, host));
     // nothing below runs on a refused mesh: the kernels that follow index with the corners and shift by the levels
-    if (host[5]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: a vertex level is not in 0..%d", ASR_MAX_LEVEL);
-    if (host[6]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: vertex outside the frame (or not finite)");
-    if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: triangle index out of range");
+    if (host[F_BAD_LEVEL]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: a vertex level is not in 0..%d", ASR_MAX_LEVEL);
+    if (host[F_OUTSIDE]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: vertex outside the frame (or not finite)");
+    if (host[F_BAD_INDEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: triangle index out of range");
     st.nv = nv;
     if (nt == 0) {  // no triangle: no output vertex, vertex_map is all -1
         st.kind = 3;
@@ -1503,9 +1503,9 @@ int asr_mesh_sample(asr_hip_context* ctx, const float* vertices, i64 nv, const i
         ASR_CHECK_LAUNCH(ctx);
         ASR_TRY(scan_f64_inclusive(ctx, ctx->scratch, area, prefix, nt));
         ASR_HIP_CHECK(ctx, hipMemcpyAsync(&total, prefix + (nt - 1), sizeof(double), hipMemcpyDeviceToHost, s));
-        int host[16];
+        HostFlags host;
         ASR_TRY(read_flags(ctx, host));
-        if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_sample: triangle index out of range");
+        if (host[F_BAD_INDEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_sample: triangle index out of range");
     }
     if (num_samples == 0) return ASR_HIP_OK;
     if (nt <= 0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_sample: no triangles to sample");
@@ -1524,7 +1524,7 @@ struct EdgeTable {
     i64* start = nullptr;   // [edges + 1] first side of every edge
     i64* count = nullptr;   // the number of edges, on the device
 };
-// sorts the sides of the triangles and finds the runs; nothing is read back (flags[4]: a corner out of range)
+// sorts the sides of the triangles and finds the runs; nothing is read back (flags[F_BAD_INDEX]: a corner out of range)
 int edge_table(asr_hip_context* ctx, const int32_t* triangles, i64 nt, i64 nv, ull* degenerate, EdgeTable& et) {
     hipStream_t s = ctx->stream;
     const i64 nq = 3 * nt;
@@ -1551,7 +1551,7 @@ int edge_table(asr_hip_context* ctx, const int32_t* triangles, i64 nt, i64 nv, u
     return ASR_HIP_OK;
 }
 // the edge count and the flag block in one wait
-int read_count_and_flags(asr_hip_context* ctx, const i64* count, i64* host_count, int* host_flags) {
+int read_count_and_flags(asr_hip_context* ctx, const i64* count, i64* host_count, HostFlags& host_flags) {
     ASR_HIP_CHECK(ctx, hipMemcpyAsync(host_count, count, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
     return read_flags(ctx, host_flags);
 }
@@ -1571,9 +1571,9 @@ int asr_mesh_edges_count(asr_hip_context* ctx, const int32_t* triangles, i64 nt,
     EdgeTable et;
     ASR_TRY(edge_table(ctx, triangles, nt, nv, nullptr, et));
     i64 ne = 0;
-    int host[16];
+    HostFlags host;
     ASR_TRY(read_count_and_flags(ctx, et.count, &ne, host));
-    if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_edges: triangle index out of range");
+    if (host[F_BAD_INDEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_edges: triangle index out of range");
     st.kind = 4;
     st.num_edges = *num_edges = ne;
     st.e_keys = et.keys;
@@ -1634,10 +1634,10 @@ int asr_mesh_topology_report(asr_hip_context* ctx, const int32_t* triangles, i64
         ASR_CHECK_LAUNCH(ctx);
     }
     ull h[TOPO_COUNTERS];
-    int host[16];
+    HostFlags host;
     ASR_HIP_CHECK(ctx, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, s));
     ASR_TRY(read_flags(ctx, host));
-    if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_topology: triangle index out of range");
+    if (host[F_BAD_INDEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_topology: triangle index out of range");
     out->degenerate_triangles = (i64)h[TOPO_DEGENERATE];
     out->triangles = nt - out->degenerate_triangles;
     out->edges = (i64)h[TOPO_EDGES];
@@ -1665,9 +1665,9 @@ int asr_mesh_smooth(asr_hip_context* ctx, const float* vertices, i64 nv, const i
     EdgeTable et;
     ASR_TRY(edge_table(ctx, triangles, nt, nv, nullptr, et));
     i64 ne = 0;
-    int host[16];
+    HostFlags host;
     ASR_TRY(read_count_and_flags(ctx, et.count, &ne, host));
-    if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: triangle index out of range");
+    if (host[F_BAD_INDEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: triangle index out of range");
     // vertex -> neighbour rows: both directions of every edge, sorted; an entry is (neighbour << 1) | feature
     const i64 np = 2 * ne;
     MESH_ALLOC(rs, i64, nv + 1);
@@ -1710,7 +1710,7 @@ int asr_mesh_smooth(asr_hip_context* ctx, const float* vertices, i64 nv, const i
     ASR_CHECK_LAUNCH(ctx);
     i64 nlong = 0;
     ASR_TRY(read_count_and_flags(ctx, loff + nv, &nlong, host));
-    if (host[7]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: a vertex is not finite");
+    if (host[F_BAD_VERTEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: a vertex is not finite");
     int cur = 0;
     for (int it = 0; it < iterations; ++it)
         for (int half = 0; half < (mu != 0.0 ? 2 : 1); ++half) {
@@ -1805,14 +1805,14 @@ int asr_mesh_fill_holes_count(asr_hip_context* ctx, const float* vertices, i64 n
     // the one read-back: counters, sizes and flags
     ull h[FILL_COUNTERS];
     i64 sizes[3] = {0, 0, 0};
-    int host[16];
+    HostFlags host;
     ASR_HIP_CHECK(ctx, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, s));
     ASR_HIP_CHECK(ctx, hipMemcpyAsync(&sizes[0], hub_off + nv, sizeof(i64), hipMemcpyDeviceToHost, s));
     ASR_HIP_CHECK(ctx, hipMemcpyAsync(&sizes[1], tri_off + nv, sizeof(i64), hipMemcpyDeviceToHost, s));
     ASR_HIP_CHECK(ctx, hipMemcpyAsync(&sizes[2], long_off + nv, sizeof(i64), hipMemcpyDeviceToHost, s));
     ASR_TRY(read_flags(ctx, host));
-    if (host[4]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes: triangle index out of range");
-    if (host[7]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes: a vertex of a filled rim is not finite");
+    if (host[F_BAD_INDEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes: triangle index out of range");
+    if (host[F_BAD_VERTEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes: a vertex of a filled rim is not finite");
     if (nv + sizes[0] >= (i64(1) << 31) || nt + sizes[1] >= (i64(1) << 31) / 3)
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes: the filled mesh does not fit 32-bit indices");
     report->rims = (i64)h[FILL_RIMS];

@@ -11,6 +11,45 @@ namespace asr_prim {
 // next block (fresh_flags) instead of clearing the one block there used to be -- twenty fill launches per geometry build,
 // each a dependent launch in one of its two chains.  The pool is cleared again, on the context's stream, when it is used up.
 constexpr int FLAG_BLOCK = 64, FLAG_BLOCKS = 512;
+// The slots of a block, one per meaning (kernels: cnt[F_...], host: HostFlags[F_...]) and the passes that write them.
+// read_flags copies the first FLAG_READ ints; the cell counts per level lie behind them and are copied by their reader.
+enum Flag : int {
+    F_ENTRIES = 0,         // octree / grow: entries of the node list (insert_with_ancestors, k_grow_init, k_grow_insert)
+    F_OVERFLOW = 1,        // a hash table or list lost a key: octree, grow, key maps, cell table, mask set, dual-cell map
+    F_MASKS = 2,           // row regrouping: number of distinct slot masks (k_rg_mask_collect)
+    F_BAD_KEY = 3,         // bad location code (k_check_keys) / bad row list (k_check_rows)
+    F_BAD_INDEX = 4,       // mesh: a corner index out of range (contour, components, simplify, sample, adjacency, fill_holes)
+    F_BAD_LEVEL = 5,       // mesh simplify: a vertex level out of range (k_simp_keys)
+    F_LEVEL_MIN = 6,       // smallest / ...
+    F_LEVEL_MAX = 7,       // ... largest query level (k_query_levels, k_attr_levels); initialised together
+    F_POINT_LEVEL = 8,     // presort: finest level a point can be inserted on (k_finest_point_level)
+    F_ROOT = 9,            // octree: the root was inserted (insert_with_ancestors)
+    F_HEAVY = 10,          // radius search: number of heavy rows (k_radius_query)
+    F_NONFINITE = 11,      // non-finite points / radii (k_octree_insert_points, k_grow_init, k_point_codes)
+    F_KNN_CELLS = 12,      // kNN: occupied finest-level cells (k_cell_list) / ...
+    F_KNN_FALLBACK = 13,   // ... points left to the wave-per-point kernel (k_knn_cells); cleared together
+    F_MAX_CELL_POP = 14,   // kNN / nearest: largest population of a finest-level cell (k_max_cell_pop)
+    F_MARGIN_PAIRS = 15,   // aligned radius search: pairs in the rounding margin (k_radius_extras, k_radius_query)
+    F_DUAL_FAN = 16,       // contouring: more than 29 dual cells round an edge (k_contour_edges)
+    F_DUAL_SORT = 17,      // contouring: cannot sort the duals round an edge (k_contour_edges)
+    F_OUTSIDE = 18,        // mesh simplify: a vertex outside the frame or not finite (k_simp_keys)
+    F_BAD_VERTEX = 19,     // mesh smooth / fill_holes: a vertex is not finite (k_smooth_load, k_fill_keys)
+    F_KEY_BITS = 20,       // octree: bits of the longest key of the node list (k_list_key_bits)
+    F_DUAL_KEY = 21,       // dual cells: no leaf found for a corner (k_dual_fill)
+    F_CELLS = 22,          // cell table: cells of all counted levels (k_cell_bounds<true>)
+    F_COUNT
+};
+constexpr int FLAG_READ = 32;        // ints read_flags copies to the host
+constexpr int FLAG_LEVEL_CELLS = 32; // first of the ASR_MAX_LEVEL + 1 cell counts per level (k_cell_bounds<true>)
+static_assert(F_COUNT <= FLAG_READ, "read_flags must cover every slot");
+static_assert(FLAG_READ <= FLAG_LEVEL_CELLS && FLAG_LEVEL_CELLS + ASR_MAX_LEVEL + 1 <= FLAG_BLOCK,
+              "the per-level cell counts lie behind the slots, inside the block");
+static_assert(F_LEVEL_MAX == F_LEVEL_MIN + 1, "query_level_range sets both with one copy");
+static_assert(F_KNN_FALLBACK == F_KNN_CELLS + 1, "asr_geom_knn clears both with one memset");
+struct HostFlags {
+    int v[FLAG_READ];
+    int operator[](Flag f) const { return v[f]; }
+};
 static inline int ensure_flags(asr_hip_context* ctx) {
     if (!ctx->d_flags_base) {
         ASR_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_flags_base, (size_t)FLAG_BLOCK * FLAG_BLOCKS * sizeof(int)));
@@ -30,15 +69,9 @@ static inline int fresh_flags(asr_hip_context* ctx) {
     ctx->d_flags = ctx->d_flags_base + (size_t)FLAG_BLOCK * ctx->flags_next++;
     return ASR_HIP_OK;
 }
-static inline int read_flags(asr_hip_context* ctx, int* host) {
-    ASR_HIP_CHECK(ctx, hipMemcpyAsync(host, ctx->d_flags, 16 * sizeof(int), hipMemcpyDeviceToHost,
+static inline int read_flags(asr_hip_context* ctx, HostFlags& host) {
+    ASR_HIP_CHECK(ctx, hipMemcpyAsync(host.v, ctx->d_flags, FLAG_READ * sizeof(int), hipMemcpyDeviceToHost,
                                       ctx->stream));
-    ASR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return ASR_HIP_OK;
-}
-static inline int set_flag(asr_hip_context* ctx, int which, int value) {
-    ASR_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_flags + which, &value, sizeof(int),
-                                      hipMemcpyHostToDevice, ctx->stream));
     ASR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return ASR_HIP_OK;
 }
