@@ -177,7 +177,7 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
                         octree_max_depth=21, contouring_value_threshold=1.0,
                         keep_n_connected_components=2**63 - 1, minimum_component_size=3, *, weights=None,
                         precision="f32", vertex_normals=False, point_attributes=None, simplify=0, smooth=0,
-                        fill_holes=0):
+                        fill_holes=0, thin=0.0):
     """module.cpp:58-109,291-346 -> asr::ReconstructSurface (cpp/lib/asr.cpp:95-349): pre-filter,
     implicit values, dual contouring, component filter; every stage on the MI355X.
     `weights` (keyword only) replaces the reference's bundled model.pt, see _load_weights.
@@ -197,8 +197,15 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
     vertex_normals and point_attributes.
     `fill_holes` (keyword only): m > 0 closes every simple boundary rim of at most m edges (3 <= m <= 2^20) with a fan
     around the mean of its vertices (asr_hip.ops.mesh_fill_holes), after simplify and before smooth; longer rims, the
-    outer border of an open scan among them, stay open."""
+    outer border of an open scan among them, stay open.
+    `thin` (keyword only): a cell size s > 0 merges the cloud first, before the pre-filter, exactly as
+    merge_points(points, normals, radii, point_attributes, cell_size=s) does: one point per occupied cell (and side) of
+    the octree level whose voxel size lies in [s, 2 s).  Given radii and point_attributes are averaged alike; without
+    given radii they are estimated on the merged cloud.  0 (default): the cloud is taken as it is."""
     from asr_hip.pipeline import ImplicitPipeline
+    thin = float(thin)
+    if not (np.isfinite(thin) and thin >= 0):
+        raise ValueError("thin must be a cell size >= 0 (0: off)")
     fill_holes = _ops.check_fill_arguments(fill_holes) if fill_holes != 0 else 0
     simplify = int(simplify)
     if simplify < 0:
@@ -226,6 +233,13 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
             raise ValueError("point_attributes must have shape [num_points] or [num_points, C]")
     if points.shape[0] == 0:
         raise RuntimeError("points is null!\n")
+    if thin > 0:
+        merged = merge_points(points, normals, radii if radii.shape[0] else None, point_attributes, cell_size=thin)
+        points, normals, point_attributes = merged["points"], merged["normals"], merged["attributes"]
+        if radii.shape[0]:
+            radii = merged["radii"]
+        if points.shape[0] == 0:
+            raise RuntimeError("no points left after thinning")
     # preprocess (asr.cpp:116-135)
     _lib.library_print("preprocessing\n", _lib.PRINT_LEVELS["INFO"])  # asr.cpp:117
     tree = KDTree(points)
@@ -324,6 +338,71 @@ def simplify_mesh(vertices, triangles, cell_size, return_map=False):
     if return_map:
         result["vertex_map"] = out[2].cpu().numpy()
     return result
+
+
+def merge_points(points, normals=None, radii=None, attributes=None, cell_size=None, radius_factor=None, split_sides=True):
+    """Not in the reference's module.  Reduces a point cloud before the reconstruction (asr_hip.ops.points_merge): all
+    points inside one octree cell become one point -- the mean position, radius and attributes ([N] or [N,C], C <= 16)
+    of its members and their normalised normal sum.  Overlapping scans so stop doubling the density.  The octree frame
+    is the one around the bounding box of the FINITE points (with KDTree's margin); points that are not finite are
+    dropped.  Exactly one of
+      cell_size      one grid for the whole cloud: the deepest level whose voxel size is >= cell_size.  THE CELL ACTUALLY
+                     USED IS THAT VOXEL SIZE, between cell_size and twice cell_size (the root cube when cell_size exceeds
+                     it); it is returned as "cell_size".
+      radius_factor  (needs radii) point i is merged on the level the octree build selects for a point of radius
+                     radius_factor * radii[i]: dense regions are thinned on finer cells than sparse ones.
+    split_sides (ignored without normals): the members of a cell whose normal points against that of the cell's first
+    member form a cluster of their own, so the two faces of a thin wall are not averaged into one.
+    -> {'points': f32 [M,3], 'normals': f32 [M,3] or None, 'radii': f32 [M] or None, 'attributes': f32 [M,C] or None,
+    'counts': int32 [M], 'cluster': int32 [N] (the output point of every input point, -1: dropped), 'report': dict of
+    ints (clusters, dropped, largest_cluster, split_cells), 'cell_size': float or None (radius_factor)}."""
+    if (cell_size is None) == (radius_factor is None):
+        raise ValueError("give exactly one of cell_size and radius_factor")
+    size = float(cell_size if cell_size is not None else radius_factor)
+    if not (np.isfinite(size) and size > 0):
+        raise ValueError("%s must be a positive number" % ("cell_size" if cell_size is not None else "radius_factor"))
+    if radius_factor is not None and radii is None:
+        raise ValueError("radius_factor needs radii")
+    points = _f32(points, "points", "[N,3]", 2, 3)
+    n = points.shape[0]
+    if normals is not None:
+        normals = _f32(normals, "normals", "[N,3]", 2, 3)
+    if radii is not None:
+        radii = _f32(radii, "radii", "[N]", 1)
+    if attributes is not None:
+        try:
+            attributes = np.ascontiguousarray(attributes, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("attributes must be convertible to float32") from None
+    split_sides = bool(split_sides) and normals is not None
+    _ops.check_merge_arguments(points, normals, radii, attributes, 0, None, split_sides)
+    finite = np.isfinite(points).all(1)
+    if not finite.any():
+        raise ValueError("no finite point")
+    frame = _margin_frame(points[finite])
+    dev = torch.device("cuda")
+    t = lambda a: None if a is None else torch.from_numpy(a).to(dev)  # noqa: E731
+    points_dev, radii_dev = t(points), t(radii)
+    level, levels, used = None, None, None
+    if cell_size is not None:
+        level = 0
+        while level < _lib.ASR_MAX_LEVEL and frame.voxel_size[level + 1] >= size:
+            level += 1
+        used = float(frame.voxel_size[level])
+    else:
+        # the level is the position of the key's marker bit (3 l); a point that will be dropped: level 0
+        keys = _ops.point_keys(frame, points_dev, radii_dev * size, 1.0, _lib.ASR_MAX_LEVEL).cpu().numpy().view(np.uint64)
+        lv = np.zeros(n, np.int8)
+        for l in range(1, _lib.ASR_MAX_LEVEL + 1):
+            lv[keys >= np.uint64(1 << (3 * l))] = l
+        lv[~finite] = 0
+        levels = torch.from_numpy(lv).to(dev)
+    p2, n2, r2, a2, cluster, counts, report = _ops.points_merge(
+        frame, points_dev, t(normals), radii_dev, t(attributes), level=level, levels=levels, split_sides=split_sides,
+        return_map=True, return_counts=True, return_report=True)
+    host = lambda a: None if a is None else a.cpu().numpy()  # noqa: E731
+    return {"points": host(p2), "normals": host(n2), "radii": host(r2), "attributes": host(a2), "counts": host(counts),
+            "cluster": host(cluster), "report": report, "cell_size": used}
 
 
 def smooth_mesh(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, boundary="along"):

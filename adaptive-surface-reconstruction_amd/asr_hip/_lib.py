@@ -12,6 +12,8 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "csrc", "libasr_hip.so")
 
 ASR_MAX_LEVEL = 21
 ASR_NUM_GRIDS = 5
+ASR_MAX_ATTRIBUTE_CHANNELS = 16
+ASR_MERGE_LONG_CLUSTER = 128  # points merge: clusters with more members are summed by a workgroup, not by one thread
 CONV16_F16 = 1      # ASR_CONV16_F16: f16 activations + weights, f32 accumulate (config C5)
 CONV16_BF16X3 = 2   # ASR_CONV16_BF16X3: exact three-way bf16 split, fp32-class results
 CONV16_F16X2 = 3    # ASR_CONV16_F16X2: scaled two-way f16 split, fp32-class results from three MFMAs per product
@@ -145,6 +147,10 @@ class MeshFillReport(ctypes.Structure):
         "rims", "filled", "too_long", "not_simple", "new_vertices", "new_triangles")]
 
 
+class PointsMergeReport(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int64) for name in ("clusters", "dropped", "largest_cluster", "split_cells")]
+
+
 # every symbol declared in include/asr_hip.h (tests/test_abi.py checks the list against the header)
 EXPORTS = [
     "asr_hip_context_create", "asr_hip_context_destroy", "asr_hip_context_set_stream",
@@ -166,6 +172,7 @@ EXPORTS = [
     "asr_hip_mesh_simplify_count", "asr_hip_mesh_simplify_fill",
     "asr_hip_mesh_edges_count", "asr_hip_mesh_edges_fill", "asr_hip_mesh_topology", "asr_hip_mesh_smooth",
     "asr_hip_mesh_fill_holes_count", "asr_hip_mesh_fill_holes_fill",
+    "asr_hip_points_merge_count", "asr_hip_points_merge_fill",
     "asr_hip_implicit_build",
     "asr_hip_implicit_network", "asr_hip_implicit_aggregate", "asr_hip_implicit_forward", "asr_hip_implicit_get",
     "asr_hip_implicit_stage_ms", "asr_hip_implicit_query",
@@ -198,7 +205,8 @@ def load():
                           ("asr_weight", Weight), ("asr_implicit_params", ImplicitParams),
                           ("asr_implicit_sizes", ImplicitSizes), ("asr_shard_comm", ShardComm),
                           ("asr_shard_stats", ShardStats), ("asr_mesh_topology", MeshTopology),
-                          ("asr_mesh_fill_report", MeshFillReport)):
+                          ("asr_mesh_fill_report", MeshFillReport),
+                          ("asr_points_merge_report", PointsMergeReport)):
             if lib.asr_hip_struct_size(name.encode()) != ctypes.sizeof(cls):
                 raise AsrHipError("ABI mismatch: struct %s has a different size in libasr_hip.so"
                                   % name)
@@ -220,8 +228,13 @@ def load():
         lib.asr_hip_mesh_fill_holes_count.argtypes = [vp, vp, i64, vp, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
                                                       ctypes.POINTER(MeshFillReport)]
         lib.asr_hip_mesh_fill_holes_fill.argtypes = [vp, vp, vp]
+        lib.asr_hip_points_merge_count.argtypes = [vp, ctypes.POINTER(OctreeFrame), vp, i64, vp, vp, vp, ctypes.c_int, vp,
+                                                   ctypes.c_int, ctypes.c_int, ctypes.POINTER(i64),
+                                                   ctypes.POINTER(PointsMergeReport)]
+        lib.asr_hip_points_merge_fill.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         for name in ("asr_hip_mesh_edges_count", "asr_hip_mesh_edges_fill", "asr_hip_mesh_topology", "asr_hip_mesh_smooth",
-                     "asr_hip_mesh_fill_holes_count", "asr_hip_mesh_fill_holes_fill"):
+                     "asr_hip_mesh_fill_holes_count", "asr_hip_mesh_fill_holes_fill", "asr_hip_points_merge_count",
+                     "asr_hip_points_merge_fill"):
             getattr(lib, name).restype = ctypes.c_int
         _lib = lib
     return _lib

@@ -957,6 +957,83 @@ def mesh_fill_holes(vertices, triangles, max_edges, return_report=False, ctx=Non
     return v2, t2
 
 
+def _shape(t):
+    return tuple(t.shape) if hasattr(t, "shape") else tuple(torch.as_tensor(t).shape)
+
+
+def check_merge_arguments(points, normals, radii, attributes, level, levels, split_sides):
+    """the shapes and options of points_merge, or ValueError; no GPU involved -> (n, c)"""
+    shape = _shape(points)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError("points must have shape [N,3]")
+    n = shape[0]
+    if n >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 points")
+    if normals is not None and _shape(normals) != (n, 3):
+        raise ValueError("normals must have shape [N,3]")
+    if radii is not None and _shape(radii) != (n,):
+        raise ValueError("radii must have shape [N]")
+    c = 0
+    if attributes is not None:
+        shape = _shape(attributes)
+        if len(shape) == 1:
+            shape = shape + (1,)
+        if len(shape) != 2 or shape[0] != n:
+            raise ValueError("attributes must have shape [N] or [N,C]")
+        c = shape[1]
+        if not 1 <= c <= _lib.ASR_MAX_ATTRIBUTE_CHANNELS:
+            raise ValueError("%d attribute channels, supported are 1 to %d" % (c, _lib.ASR_MAX_ATTRIBUTE_CHANNELS))
+    if (level is None) == (levels is None):
+        raise ValueError("give exactly one of level and levels")
+    if level is not None and (isinstance(level, bool) or int(level) != level or not 0 <= int(level) <= _lib.ASR_MAX_LEVEL):
+        raise ValueError("level must be an integer in 0..%d" % _lib.ASR_MAX_LEVEL)
+    if levels is not None and _shape(levels) != (n,):
+        raise ValueError("levels must have shape [N]")
+    if split_sides and normals is None:
+        raise ValueError("split_sides needs normals")
+    return n, c
+
+
+def points_merge(frame, points, normals=None, radii=None, attributes=None, level=None, levels=None, split_sides=False,
+                 return_map=False, return_counts=False, return_report=False, ctx=None):
+    """One point per occupied octree cell (asr_hip_points_merge_count / _fill; the contract is in include/asr_hip.h): all
+    points in one cell of `frame` at `level` (0..21, one for the whole cloud) or at `levels` (int8-convertible [N], one per
+    point) become one point -- position, radius and attributes [N] or [N,C] (C <= 16) are the f64 mean of the members,
+    the normal their normalised sum.  split_sides=True (needs normals) keeps the members whose normal points against
+    that of the cell's first member as a cluster of their own: the two faces of a thin wall stay apart.  Points that are
+    not finite or lie outside the frame's root cube are dropped.  Clusters come in ascending key order, the same bits on
+    every run.  Exactly one of level and levels must be given.
+    -> (points f32 [M,3], normals f32 [M,3] or None, radii f32 [M] or None, attributes f32 [M,C] or None), followed by
+    cluster int32 [N] (the output point of every input point, -1: dropped) with return_map, counts int32 [M] with
+    return_counts and a dict of ints (clusters, dropped, largest_cluster, split_cells) with return_report."""
+    n, c = check_merge_arguments(points, normals, radii, attributes, level, levels, split_sides)
+    points = _dev(points, torch.float32)
+    normals = _dev(normals, torch.float32) if normals is not None else None
+    radii = _dev(radii, torch.float32) if radii is not None else None
+    if attributes is not None:
+        attributes = _dev(attributes, torch.float32).reshape(n, c)
+    if levels is not None:
+        levels = _dev(levels, torch.int8)
+    dev = _same_device(points, normals, radii, attributes, levels)
+    ctx = ctx or context(dev)
+    m, report = i64(0), _lib.PointsMergeReport()
+    ctx.call("asr_hip_points_merge_count", ctypes.byref(frame), ptr(points), i64(n), ptr(normals), ptr(radii),
+             ptr(attributes), int(c), ptr(levels), int(level) if levels is None else 0, int(bool(split_sides)),
+             ctypes.byref(m), ctypes.byref(report))
+    m = m.value
+    p2 = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    n2 = torch.empty((m, 3), dtype=torch.float32, device=dev) if normals is not None else None
+    r2 = torch.empty(m, dtype=torch.float32, device=dev) if radii is not None else None
+    a2 = torch.empty((m, c), dtype=torch.float32, device=dev) if attributes is not None else None
+    counts = torch.empty(m, dtype=torch.int32, device=dev) if return_counts else None
+    cluster = torch.empty(n, dtype=torch.int32, device=dev) if return_map else None
+    ctx.call("asr_hip_points_merge_fill", ptr(p2), ptr(n2), ptr(r2), ptr(a2), ptr(counts), ptr(cluster))
+    out = (p2, n2, r2, a2) + ((cluster,) if return_map else ()) + ((counts,) if return_counts else ())
+    if return_report:
+        out += ({name: int(getattr(report, name)) for name, _ in _lib.PointsMergeReport._fields_},)
+    return out
+
+
 def decode_mlp_at(code, shifts, w1, b1, w2, b2, w3, rows=None, voxel_sizes=None, gradient=False):
     """UNet5.decode(shifts, code[rows]) (net_definitions_torch.py:655-666) -> values [M,2]; with gradient=True
     (values, grad [M,3]) where grad is decode_with_gradient's d values[:,0] / d shift (:668-686, unscaled).

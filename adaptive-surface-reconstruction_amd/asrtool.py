@@ -4,6 +4,8 @@ reference (cpp/bin/main.cpp:114-177: `asrtool --in point_cloud.ply --out mesh.pl
 
     python adaptive-surface-reconstruction_amd/asrtool.py --in scan.ply --out mesh.ply [--weights model.pt] [--precision NAME]
                                                           [--normals] [--colors] [--simplify K] [--smooth N] [--fill-holes N]
+                                                          [--thin SIZE]
+    python adaptive-surface-reconstruction_amd/asrtool.py --thin-cloud scan.ply out.ply --cell SIZE
     python adaptive-surface-reconstruction_amd/asrtool.py --compare mesh.ply reference.ply [--samples N] [--thresholds a,b,...] [--seed S]
     python adaptive-surface-reconstruction_amd/asrtool.py --decimate mesh.ply out.ply --cell SIZE
     python adaptive-surface-reconstruction_amd/asrtool.py --smooth-mesh mesh.ply out.ply [--iterations N] [--boundary free|pinned|along]
@@ -34,6 +36,11 @@ Options:
               describe the smoothed vertices
     --fill-holes N  Closes every simple boundary rim of at most N edges (3 <= N <= 1048576) with a fan around the mean of its
               vertices, after --simplify and before --smooth; longer rims, the outer border of an open scan among them, stay open
+    --thin SIZE  Merges the input points inside one cell of a regular grid (and on one side of it: normals that point against
+              each other stay apart) into their mean before anything else.  The cell used is the voxel size of the octree
+              level around the cloud that is >= SIZE and < 2 SIZE.  Radii and colours are averaged with the points
+    --thin-cloud IN.ply OUT.ply --cell SIZE  Instead of reconstructing: writes the cloud merged as --thin SIZE does, with its
+              normals and, where the input has them, radii and colours; prints the cell size used
     --fill-mesh MESH.ply OUT.ply --max-edges N  Instead of reconstructing: closes the holes of at most N edges of an existing
               mesh and prints one JSON line with the counts (rims, filled, too_long, not_simple, new_vertices, new_triangles).
               Each new hub vertex gets the mean of the normals and colours of its rim
@@ -142,6 +149,52 @@ def _decimate(argv):
     print("wrote %s: %d -> %d vertices, %d -> %d triangles, cell size %g (level %d)"
           % (paths[1], len(v), len(result["vertices"]), len(t), len(result["triangles"]), result["cell_size"],
              result["level"]))
+    return 0
+
+
+def _size(text):
+    """the SIZE of --thin / --cell, or None when it is no positive finite number"""
+    try:
+        size = float(text)
+    except (TypeError, ValueError):
+        return None
+    return size if 0 < size < float("inf") else None
+
+
+def _thin_cloud(argv):
+    """--thin-cloud IN.ply OUT.ply --cell SIZE: 0, or a message on stderr and 1 (before any GPU work) when something is
+    wrong"""
+    i = argv.index("--thin-cloud")
+    paths = argv[i + 1:i + 3]
+    if len(paths) < 2 or any(p.startswith("--") for p in paths):
+        sys.stderr.write("asrtool: --thin-cloud needs two files: IN.ply OUT.ply\n")
+        return 1
+    cell = _size(_option(argv, "--cell"))
+    if cell is None:
+        sys.stderr.write("asrtool: --thin-cloud needs --cell SIZE, a positive number\n")
+        return 1
+    if not os.path.isfile(paths[0]):
+        sys.stderr.write("asrtool: --thin-cloud: no such file: %s\n" % paths[0])
+        return 1
+    from asr_hip import ply
+    try:
+        points, normals, radii = ply.read_points(paths[0])
+        colors = ply.read_point_colors(paths[0])
+    except (ValueError, IndexError, OSError) as e:
+        sys.stderr.write("asrtool: --thin-cloud: cannot read %s as a point cloud: %s\n" % (paths[0], e))
+        return 1
+    if len(points) == 0:
+        sys.stderr.write("asrtool: --thin-cloud: %s has no points\n" % paths[0])
+        return 1
+    import numpy as np
+    import adaptivesurfacereconstruction as asr
+    result = asr.merge_points(points, normals, radii if len(radii) else None,
+                              None if colors is None else colors.astype(np.float32), cell_size=cell)
+    if colors is not None:
+        colors = np.rint(np.clip(result["attributes"], 0, 255)).astype(np.uint8)
+    ply.write_points(paths[1], result["points"], result["normals"], result["radii"], colors=colors)
+    print("wrote %s: %d -> %d points (%d dropped), cell size %g"
+          % (paths[1], len(points), len(result["points"]), result["report"]["dropped"], result["cell_size"]))
     return 0
 
 
@@ -269,6 +322,8 @@ def main(argv=None):
         return _fill_mesh(argv)
     if "--topology" in argv:
         return _topology(argv)
+    if "--thin-cloud" in argv:
+        return _thin_cloud(argv)
     inp, out = _option(argv, "--in"), _option(argv, "--out")
     if inp is None or out is None:
         sys.stdout.write(HELP)
@@ -302,6 +357,12 @@ def main(argv=None):
         if fill_holes is None:
             sys.stderr.write("asrtool: --fill-holes takes a number of rim edges N, 3 <= N <= 1048576\n")
             return 1
+    thin = 0.0
+    if "--thin" in argv:  # before any GPU work
+        thin = _size(_option(argv, "--thin"))
+        if thin is None:
+            sys.stderr.write("asrtool: --thin takes a cell size SIZE, a positive number\n")
+            return 1
     from asr_hip import ply
     colors = None
     if "--colors" in argv:  # before any GPU work: a cloud without colours is an error
@@ -320,6 +381,8 @@ def main(argv=None):
         extra["smooth"] = smooth
     if fill_holes:
         extra["fill_holes"] = fill_holes
+    if thin:
+        extra["thin"] = thin
     result = asr.reconstruct_surface(points, normals, radii, weights=_option(argv, "--weights"), precision=precision,
                                      vertex_normals="--normals" in argv, **extra)
     if colors is not None:

@@ -108,6 +108,7 @@ size_t asr_hip_struct_size(const char* name) {
     if (!strcmp(name, "asr_shard_stats")) return sizeof(asr_shard_stats);
     if (!strcmp(name, "asr_mesh_topology")) return sizeof(asr_mesh_topology);
     if (!strcmp(name, "asr_mesh_fill_report")) return sizeof(asr_mesh_fill_report);
+    if (!strcmp(name, "asr_points_merge_report")) return sizeof(asr_points_merge_report);
     return 0;
 }
 
@@ -802,6 +803,29 @@ int asr_hip_mesh_fill_holes_count(asr_hip_context* ctx, const float* vertices, i
 int asr_hip_mesh_fill_holes_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out) {
     CTX_GUARD(ctx);
     return asr_mesh_fill_holes_fill(ctx, vertices_out, triangles_out);
+}
+int asr_hip_points_merge_count(asr_hip_context* ctx, const asr_octree_frame* frame, const float* points, int64_t n,
+                               const float* normals, const float* radii, const float* attributes, int c,
+                               const int8_t* levels, int level, int split_sides, int64_t* num_clusters_out,
+                               asr_points_merge_report* report) {
+    CTX_GUARD(ctx);
+    ctx->merge = AsrMergeState();
+    if (!frame || !num_clusters_out || (n > 0 && !points)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "points_merge_count: null argument");
+    if (n < 0 || n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "points_merge_count: 0 <= n < 2^31 points are required");
+    if (!levels && (level < 0 || level > ASR_MAX_LEVEL))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "points_merge_count: level %d is not in 0..%d", level, ASR_MAX_LEVEL);
+    if (split_sides != 0 && split_sides != 1) ASR_FAIL(ctx, ASR_HIP_EINVAL, "points_merge_count: split_sides must be 0 or 1");
+    if (split_sides && !normals && n > 0) ASR_FAIL(ctx, ASR_HIP_EINVAL, "points_merge_count: split_sides needs normals");
+    if (attributes && (c < 1 || c > ASR_MAX_ATTRIBUTE_CHANNELS))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "points_merge_count: %d attribute channels, supported are 1 to %d", c,
+                 ASR_MAX_ATTRIBUTE_CHANNELS);
+    return asr_points_merge_count(ctx, frame, points, n, normals, radii, attributes, attributes ? c : 0, levels, level,
+                                  split_sides, num_clusters_out, report);
+}
+int asr_hip_points_merge_fill(asr_hip_context* ctx, float* points_out, float* normals_out, float* radii_out,
+                              float* attributes_out, int32_t* counts_out, int32_t* cluster_out) {
+    CTX_GUARD(ctx);
+    return asr_points_merge_fill(ctx, points_out, normals_out, radii_out, attributes_out, counts_out, cluster_out);
 }
 
 }  // extern "C"

@@ -174,6 +174,19 @@ struct AsrPointIndex {
     int tab_lmin = 0, tab_lmax = -1, tab_lhash = 0, tab_grow = 0;
 };
 
+// asr_hip_points_merge_count -> _fill: the caller's inputs and the sorted member lists in the scratch arena
+struct AsrMergeState {
+    bool valid = false;
+    const float *points = nullptr, *normals = nullptr, *radii = nullptr, *attributes = nullptr;
+    int channels = 0;
+    i64 n = 0, clusters = 0, num_long = 0;
+    const u64* keys = nullptr;            // sorted keys, 0 for the dropped points in front
+    const int32_t* ids = nullptr;         // input index per sorted position, each cluster's members in ascending order
+    const i64* offsets = nullptr;         // exclusive scan of the cluster heads (n + 1)
+    const i64* starts = nullptr;          // first sorted position of every cluster (clusters + 1)
+    const int32_t* long_list = nullptr;   // clusters of more than ASR_MERGE_LONG_CLUSTER members, any order
+};
+
 struct asr_hip_context {
     hipStream_t stream = nullptr;
     hipEvent_t switch_ev = nullptr;  // asr_hip_context_set_stream: recorded on the old stream, awaited by the new one
@@ -243,6 +256,7 @@ struct asr_hip_context {
     unsigned* d_absmax = nullptr;  // f16x2: running maxima of the network's activation buffers; [255]: one-off inputs
     void* radius_state = nullptr;  // RadiusState of asr_geom.hip (between _count and _fill)
     void* mesh_state = nullptr;    // MeshState of asr_mesh.hip (between _count and _fill)
+    AsrMergeState merge;           // asr_points.hip (between _count and _fill)
     std::map<std::string, std::pair<const void*, size_t>> named;  // asr_hip_implicit_get
     int device = 0;                 // HIP device of this context (helper threads must select it)
     asr_hip_context* aux = nullptr;  // second stream + arenas: the aggregation search runs there, overlapped
@@ -526,6 +540,12 @@ int asr_mesh_fill_holes_count(asr_hip_context* ctx, const float* vertices, i64 n
                               int max_edges, i64* nv_out, i64* nt_out, asr_mesh_fill_report* report);
 int asr_mesh_fill_holes_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out);
 void asr_mesh_release(asr_hip_context* ctx);
+// asr_points.hip: one point per occupied octree cell (asr_hip_points_merge_count / _fill); arguments validated by the callers
+int asr_points_merge_count(asr_hip_context* ctx, const asr_octree_frame* frame, const float* points, i64 n,
+                           const float* normals, const float* radii, const float* attributes, int c, const int8_t* levels,
+                           int level, int split_sides, i64* num_clusters, asr_points_merge_report* report);
+int asr_points_merge_fill(asr_hip_context* ctx, float* points_out, float* normals_out, float* radii_out,
+                          float* attributes_out, int32_t* counts_out, int32_t* cluster_out);
 
 int asr_conv_agg_importance(asr_hip_context* ctx, const float* compat, const float* dist, i64 n,
                             float* out);

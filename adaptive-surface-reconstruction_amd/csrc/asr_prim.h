@@ -19,7 +19,7 @@ enum Flag : int {
     F_MASKS = 2,           // row regrouping: number of distinct slot masks (k_rg_mask_collect)
     F_BAD_KEY = 3,         // bad location code (k_check_keys) / bad row list (k_check_rows)
     F_BAD_INDEX = 4,       // mesh: a corner index out of range (contour, components, simplify, sample, adjacency, fill_holes)
-    F_BAD_LEVEL = 5,       // mesh simplify: a vertex level out of range (k_simp_keys)
+    F_BAD_LEVEL = 5,       // mesh simplify / points merge: a level out of range (k_simp_keys, k_merge_keys)
     F_LEVEL_MIN = 6,       // smallest / ...
     F_LEVEL_MAX = 7,       // ... largest query level (k_query_levels, k_attr_levels); initialised together
     F_POINT_LEVEL = 8,     // presort: finest level a point can be inserted on (k_finest_point_level)
@@ -37,6 +37,11 @@ enum Flag : int {
     F_KEY_BITS = 20,       // octree: bits of the longest key of the node list (k_list_key_bits)
     F_DUAL_KEY = 21,       // dual cells: no leaf found for a corner (k_dual_fill)
     F_CELLS = 22,          // cell table: cells of all counted levels (k_cell_bounds<true>)
+    F_MERGE_DROPPED = 23,  // points merge: points that are not finite or lie outside the root cube (k_merge_keys)
+    F_MERGE_SPLIT = 24,    // points merge: cells split into two sides (k_merge_cluster_heads)
+    F_MERGE_CLUSTERS = 25, // points merge: clusters (k_merge_starts) / ...
+    F_MERGE_LARGEST = 26,  // ... members of the largest one / ...
+    F_MERGE_LONG = 27,     // ... clusters longer than ASR_MERGE_LONG_CLUSTER (k_merge_stats)
     F_COUNT
 };
 constexpr int FLAG_READ = 32;        // ints read_flags copies to the host

@@ -644,6 +644,56 @@ int asr_hip_mesh_fill_holes_count(asr_hip_context* ctx, const float* vertices_de
                                   const int32_t* triangles_dev, int64_t num_triangles, int64_t max_edges,
                                   int64_t* num_vertices_out, int64_t* num_triangles_out, asr_mesh_fill_report* report);
 int asr_hip_mesh_fill_holes_fill(asr_hip_context* ctx, float* vertices_out_dev, int32_t* triangles_out_dev);
+/* ---- point merge: one point per occupied octree cell (not in the reference).
+ * Reduces a cloud before the reconstruction: all points that share a cell of the frame's octree become one point, the
+ * mean of its members.  Count / fill pair like asr_hip_mesh_simplify_*; the contract, which tests/points_merge_ref.py
+ * restates in numpy:
+ *   Inputs: points_dev [n,3]; optional (NULL: absent) normals_dev [n,3], radii_dev [n] and attributes_dev [n,c] with
+ *     1 <= c <= ASR_MAX_ATTRIBUTE_CHANNELS (c is ignored without attributes).  0 <= n < 2^31; n == 0 is valid and gives
+ *     an empty result.
+ *   Cell of point i: exactly the cell of asr_hip_mesh_simplify_*.  Its level is l_i = levels_dev[i], or `level` when
+ *     levels_dev is NULL, and must lie in 0..ASR_MAX_LEVEL (else ASR_HIP_EINVAL); with c21 = floor(p *
+ *     inv_voxel_size[21]) + offset per axis in f32 the cell is c21 >> (21 - l_i) and its key the location code of
+ *     (cell, l_i).  A point that is not finite or lies outside the root cube is DROPPED, not an error (scanner output
+ *     holds NaNs): it belongs to no cluster, its map entry is -1 and the report counts it.
+ *   Side bit (split_sides = 1 only; needs normals, else ASR_HIP_EINVAL): r is the normal of the member of the cell with
+ *     the smallest input index.  Member i has side 1 when (nx*rx + ny*ry) + nz*rz < 0, evaluated in f32 without
+ *     contraction, otherwise side 0 (a NaN product gives side 0).  The two faces of a thin wall that share a cell so
+ *     stay apart.  Without split_sides every side is 0.
+ *   Clusters: the distinct (key, side) pairs, in ascending key order and side 0 before side 1.  Cells of different
+ *     levels are different clusters, even when one contains the other.
+ *   Per cluster, its members taken in ascending input index: counts_out_dev = their number (int32); position, radius
+ *     and every attribute channel = the mean, summed in f64, divided by the count in f64 and rounded once to f32;
+ *     normal = the f64 sum of the members' normals as given, divided by its f64 length sqrt((sx*sx + sy*sy) + sz*sz)
+ *     -- when that length is 0 or not finite, the normal of the cluster's first member, bit for bit.  A cluster of
+ *     exactly one member copies all of that member's bits.  Non-finite radii, normals and attributes propagate into
+ *     their cluster; only positions decide dropping.
+ *   Summation: a cluster of at most ASR_MERGE_LONG_CLUSTER members is one sequential f64 chain in ascending input
+ *     index.  A longer one is summed by a workgroup of 256 threads: thread t adds the members t, t + 256, ... of the
+ *     sorted member list in order, the 64 partial sums of each wave are added pairwise (xor 32, 16, ... 1), and the four
+ *     wave sums as (w0 + w1) + (w2 + w3).  No floating-point atomics: the same inputs give the same bits on every run.
+ *   Accuracy: an output value is the f32 rounding of a value within members * 2^-53 * max|x| of the exact mean, so it
+ *     differs from the correctly rounded mean by at most 1 f32 ulp for clusters of up to 2^20 members whose mean is not
+ *     cancelled (|mean| of the order of max|x|); the same holds for the normal when |sum n| >= 1e-3 sum |n|.
+ *   A merged position is NOT guaranteed to fall back into its own cell: the f32 cell arithmetic is not convex to the
+ *     last bit.  It lies in the cell's box within 2^-22 * max|corner| per axis.
+ *   cluster_out_dev [n] (int32): the output index of each point's cluster, -1 for a dropped point.
+ *   Report: clusters, dropped points, members of the largest cluster, cells that were split into two sides.
+ * _count enqueues the key pass, one stable radix sort of (key, index) -- its last bit taken from `level`, all 64 bits
+ * with levels_dev --, the side partition and the cluster scan, and reads the cluster count, the error flags and the
+ * report back once; scratch comes from the context arena and stays valid until _fill, which must be the next call of
+ * this family on the context and runs the reduction.  The input arrays must still be alive then.  Every output pointer
+ * of _fill, and report, may be NULL; an output whose input was not given is not written. */
+#define ASR_MERGE_LONG_CLUSTER 128
+typedef struct asr_points_merge_report {
+    int64_t clusters, dropped, largest_cluster, split_cells;
+} asr_points_merge_report;
+int asr_hip_points_merge_count(asr_hip_context* ctx, const asr_octree_frame* frame, const float* points_dev, int64_t n,
+                               const float* normals_dev, const float* radii_dev, const float* attributes_dev, int c,
+                               const int8_t* levels_dev, int level, int split_sides, int64_t* num_clusters_out,
+                               asr_points_merge_report* report);
+int asr_hip_points_merge_fill(asr_hip_context* ctx, float* points_out_dev, float* normals_out_dev, float* radii_out_dev,
+                              float* attributes_out_dev, int32_t* counts_out_dev, int32_t* cluster_out_dev);
 /* (asr_hip_implicit_query, the whole-path query on the last forward, is declared after asr_hip_implicit_stage_ms) */
 
 /* ---- whole path: the section of asr::ReconstructSurface between the pre-filter and the
