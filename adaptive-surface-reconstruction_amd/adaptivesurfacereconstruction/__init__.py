@@ -172,12 +172,12 @@ def _load_weights(weights):
     return weights
 
 
-def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point_radius_scale=1.0,
+def reconstruct_surface(points, normals=None, radii=np.empty((0,), np.float32), point_radius_scale=1.0,
                         density_percentile_threshold=10.0, point_radius_estimation_knn=24,
                         octree_max_depth=21, contouring_value_threshold=1.0,
                         keep_n_connected_components=2**63 - 1, minimum_component_size=3, *, weights=None,
                         precision="f32", vertex_normals=False, point_attributes=None, simplify=0, smooth=0,
-                        fill_holes=0, thin=0.0):
+                        fill_holes=0, thin=0.0, normal_k=16, viewpoint=None):
     """module.cpp:58-109,291-346 -> asr::ReconstructSurface (cpp/lib/asr.cpp:95-349): pre-filter,
     implicit values, dual contouring, component filter; every stage on the MI355X.
     `weights` (keyword only) replaces the reference's bundled model.pt, see _load_weights.
@@ -201,8 +201,14 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
     `thin` (keyword only): a cell size s > 0 merges the cloud first, before the pre-filter, exactly as
     merge_points(points, normals, radii, point_attributes, cell_size=s) does: one point per occupied cell (and side) of
     the octree level whose voxel size lies in [s, 2 s).  Given radii and point_attributes are averaged alike; without
-    given radii they are estimated on the merged cloud.  0 (default): the cloud is taken as it is."""
+    given radii they are estimated on the merged cloud.  0 (default): the cloud is taken as it is.
+    `normals` None: the cloud has no (or no oriented) normals and they are estimated, after `thin` and before the
+    pre-filter, exactly as estimate_normals(points, normal_k, viewpoint) does; points without a usable estimate
+    (ok == False) are dropped with their radii and attributes.  `normal_k` (keyword only, 3..64) and `viewpoint`
+    (keyword only, [3], or [N,3] for the cloud as it is after thin; None: propagation) are ignored when normals are given."""
     from asr_hip.pipeline import ImplicitPipeline
+    if normals is None:
+        normal_k = _ops.check_normal_k(normal_k)
     thin = float(thin)
     if not (np.isfinite(thin) and thin >= 0):
         raise ValueError("thin must be a cell size >= 0 (0: off)")
@@ -216,10 +222,13 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
     if precision not in _lib.PRECISIONS:
         raise ValueError("precision must be one of %s" % ", ".join(sorted(_lib.PRECISIONS)))
     points = _f32(points, "points", "[num_points,3]", 2, 3)
-    normals = _f32(normals, "normals", "[num_points,3]", 2, 3)
+    if normals is not None:
+        normals = _f32(normals, "normals", "[num_points,3]", 2, 3)
     radii = np.ascontiguousarray(radii, dtype=np.float32)
-    if normals.shape != points.shape:
+    if normals is not None and normals.shape != points.shape:
         raise ValueError("normals must have shape [num_points,3]")
+    if normals is None and viewpoint is not None:
+        viewpoint = _viewpoint(viewpoint, points.shape[0] if thin == 0 else None)
     if radii.ndim != 1 or radii.shape[0] not in (0, points.shape[0]):
         raise ValueError("radii must have shape [num_point3]")
     if point_attributes is not None:
@@ -240,6 +249,16 @@ def reconstruct_surface(points, normals, radii=np.empty((0,), np.float32), point
             radii = merged["radii"]
         if points.shape[0] == 0:
             raise RuntimeError("no points left after thinning")
+    if normals is None:
+        est = estimate_normals(points, normal_k, viewpoint)
+        ok = est["ok"]
+        points, normals = np.ascontiguousarray(points[ok]), np.ascontiguousarray(est["normals"][ok])
+        if radii.shape[0]:
+            radii = np.ascontiguousarray(radii[ok])
+        if point_attributes is not None:
+            point_attributes = np.ascontiguousarray(point_attributes[ok])
+        if points.shape[0] == 0:
+            raise RuntimeError("no points left after the normal estimation")
     # preprocess (asr.cpp:116-135)
     _lib.library_print("preprocessing\n", _lib.PRINT_LEVELS["INFO"])  # asr.cpp:117
     tree = KDTree(points)
@@ -304,6 +323,55 @@ def _margin_frame(points):
     lo, hi = points.min(0), points.max(0)
     m = max(1e-3, 1e-3 * float((hi - lo).max()))
     return _lib.frame_init(lo - np.float32(m), hi + np.float32(m))
+
+
+def _viewpoint(viewpoint, n):
+    """viewpoint as f32 [3] or [n,3] (n None: any number of rows), or ValueError"""
+    try:
+        v = np.ascontiguousarray(viewpoint, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("viewpoint must be convertible to float32") from None
+    if not (v.shape == (3,) or (v.ndim == 2 and v.shape[1] == 3 and (n is None or v.shape[0] == n))):
+        raise ValueError("viewpoint must have shape [3] or [N,3]")
+    if not np.isfinite(v).all():
+        raise ValueError("viewpoint must be finite")
+    return v
+
+
+def estimate_normals(points, k=16, viewpoint=None):
+    """Not in the reference's module.  Oriented normals for a cloud that has none, every stage on the
+    GPU: the exact k nearest neighbours of every point, itself included (asr_hip.ops.knn_index, 3 <= k <= 64, in the
+    octree frame around the bounding box with KDTree's margin), a PCA plane through them (ops.point_normals) and
+    consistent signs (ops.orient_normals): towards `viewpoint` ([3], the scanner's position, or [N,3], one per point)
+    or, with viewpoint None, propagated along the minimum spanning forest of the neighbour graph, each connected part
+    signed so that its highest point looks up.  Non-finite points are a ValueError.
+    -> {'normals': f32 [N,3] (zero where ok is False), 'ok': bool [N] (False: fewer than three or collinear neighbours),
+    'eigenvalues': f32 [N,3] ascending, 'variation': f32 [N] = l0 / (l0 + l1 + l2) (0 where ok is False),
+    'neighbors': int32 [N,k], 'report': dict of ints (components, flipped, skipped, rounds)}."""
+    k = _ops.check_normal_k(k)
+    points = _f32(points, "points", "[N,3]", 2, 3)
+    n = points.shape[0]
+    if n == 0:
+        raise ValueError("points is empty")
+    if not np.isfinite(points).all():
+        raise ValueError("points must be finite")
+    if viewpoint is not None:
+        viewpoint = _viewpoint(viewpoint, n)
+    frame = _margin_frame(points)
+    dev = torch.device("cuda")
+    p = torch.from_numpy(points).to(dev)
+    index, _ = _ops.knn_index(frame, p, k)
+    normals, eig, ok = _ops.point_normals(p, index, return_eigenvalues=True, return_ok=True)
+    if viewpoint is None:
+        normals, report = _ops.orient_normals(p, normals, index, return_report=True)
+    else:
+        normals, report = _ops.orient_normals(p, normals, viewpoints=torch.from_numpy(viewpoint).to(dev), return_report=True)
+    eig, ok = eig.cpu().numpy(), ok.cpu().numpy()
+    total = eig.sum(1, dtype=np.float32)
+    good = ok & (total > 0)
+    variation = np.where(good, eig[:, 0] / np.where(good, total, np.float32(1)), np.float32(0)).astype(np.float32)
+    return {"normals": normals.cpu().numpy(), "ok": ok, "eigenvalues": eig, "variation": variation,
+            "neighbors": index.cpu().numpy(), "report": report}
 
 
 def simplify_mesh(vertices, triangles, cell_size, return_map=False):
@@ -483,6 +551,13 @@ class KDTree:
         cnt = _ops.radius_neighbor_count(self._frame, self._points,
                                          torch.from_numpy(radii).to(self._points.device))
         return [int(c) for c in cnt.cpu().tolist()]
+
+    def knn(self, k):
+        """Not in the reference's module.  The k nearest points of every point of the tree, itself included, exactly
+        (brute-force result in f32, rows ordered by (squared distance, index); 1 <= k <= 64, rows of a tree with fewer
+        than k points are padded with -1 and inf) -> (index int32 [N,k], squared distance f32 [N,k])"""
+        idx, sq = _ops.knn_index(self._frame, self._points, k)
+        return idx.cpu().numpy(), sq.cpu().numpy()
 
     def nearest(self, queries):
         """Not in the reference's module.  For each query [M,3] the nearest point of the tree, exactly (brute-force

@@ -173,6 +173,7 @@ EXPORTS = [
     "asr_hip_mesh_edges_count", "asr_hip_mesh_edges_fill", "asr_hip_mesh_topology", "asr_hip_mesh_smooth",
     "asr_hip_mesh_fill_holes_count", "asr_hip_mesh_fill_holes_fill",
     "asr_hip_points_merge_count", "asr_hip_points_merge_fill",
+    "asr_hip_knn_index", "asr_hip_point_normals", "asr_hip_normals_orient",
     "asr_hip_implicit_build",
     "asr_hip_implicit_network", "asr_hip_implicit_aggregate", "asr_hip_implicit_forward", "asr_hip_implicit_get",
     "asr_hip_implicit_stage_ms", "asr_hip_implicit_query",
@@ -232,9 +233,12 @@ def load():
                                                    ctypes.c_int, ctypes.c_int, ctypes.POINTER(i64),
                                                    ctypes.POINTER(PointsMergeReport)]
         lib.asr_hip_points_merge_fill.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        lib.asr_hip_knn_index.argtypes = [vp, ctypes.POINTER(OctreeFrame), vp, i64, ctypes.c_int, vp, vp]
+        lib.asr_hip_point_normals.argtypes = [vp, vp, i64, vp, ctypes.c_int, vp, vp, vp]
+        lib.asr_hip_normals_orient.argtypes = [vp, vp, vp, i64, vp, ctypes.c_int, vp, i64, vp, vp, ctypes.POINTER(i64)]
         for name in ("asr_hip_mesh_edges_count", "asr_hip_mesh_edges_fill", "asr_hip_mesh_topology", "asr_hip_mesh_smooth",
                      "asr_hip_mesh_fill_holes_count", "asr_hip_mesh_fill_holes_fill", "asr_hip_points_merge_count",
-                     "asr_hip_points_merge_fill"):
+                     "asr_hip_points_merge_fill", "asr_hip_knn_index", "asr_hip_point_normals", "asr_hip_normals_orient"):
             getattr(lib, name).restype = ctypes.c_int
         _lib = lib
     return _lib

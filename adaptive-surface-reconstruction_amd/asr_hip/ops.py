@@ -1034,6 +1034,136 @@ def points_merge(frame, points, normals=None, radii=None, attributes=None, level
     return out
 
 
+KNN_INDEX_MAX_K = 64
+ORIENT_REPORT = ("components", "flipped", "skipped", "rounds")
+
+
+def _check_int(value, lo, hi, what):
+    try:
+        good = not isinstance(value, bool) and int(value) == value and lo <= int(value) <= hi
+    except (TypeError, ValueError):
+        good = False
+    if not good:
+        raise ValueError("%s must be an integer in %d..%d" % (what, lo, hi))
+    return int(value)
+
+
+def check_normal_k(k):
+    """the neighbour count of a normal estimate (3..64) as an int, or ValueError; no GPU involved"""
+    return _check_int(k, 3, KNN_INDEX_MAX_K, "the number of neighbours of a normal estimate")
+
+
+def check_knn_index_arguments(points, k):
+    """the shapes and ranges of knn_index, or ValueError; no GPU involved -> (n, k)"""
+    shape = _shape(points)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError("points must have shape [N,3]")
+    if not 1 <= shape[0] < 2 ** 31:
+        raise ValueError("1 <= N < 2^31 points are required")
+    return shape[0], _check_int(k, 1, KNN_INDEX_MAX_K, "k")
+
+
+def knn_index(frame, points, k):
+    """Exact k-nearest-neighbour lists (asr_hip_knn_index; the contract is in include/asr_hip.h): row i holds the k
+    smallest pairs (d2(i, j), j), the point itself included, ascending, with d2 = ((dx*dx + dy*dy) + dz*dz) in f32 -- a
+    brute-force search's result, ties to the smaller index.  1 <= k <= 64; rows of a cloud with N < k are padded with -1
+    and +inf.  The frame must contain the points.  -> (index int32 [N,k], squared distance f32 [N,k])"""
+    n, k = check_knn_index_arguments(points, k)
+    points = _dev(points, torch.float32)
+    index = torch.empty((n, k), dtype=torch.int32, device=points.device)
+    sqdist = torch.empty((n, k), dtype=torch.float32, device=points.device)
+    context(_same_device(points)).call("asr_hip_knn_index", ctypes.byref(frame), ptr(points), i64(n), k, ptr(index),
+                                       ptr(sqdist))
+    return index, sqdist
+
+
+def check_point_normals_arguments(points, index):
+    """the shapes and ranges of point_normals, or ValueError; no GPU involved -> (n, k)"""
+    shape = _shape(points)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError("points must have shape [N,3]")
+    if shape[0] >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 points")
+    ishape = _shape(index)
+    if len(ishape) != 2 or ishape[0] != shape[0]:
+        raise ValueError("index must have shape [N,k]")
+    if not 3 <= ishape[1] <= KNN_INDEX_MAX_K:
+        raise ValueError("index must have 3 to %d columns" % KNN_INDEX_MAX_K)
+    return shape[0], ishape[1]
+
+
+def point_normals(points, index, return_eigenvalues=False, return_ok=False):
+    """PCA normals over given neighbour lists (asr_hip_point_normals): index int32 [N,k] with 3 <= k <= 64, from knn_index
+    or hand-made, entries -1 skipped.  f64 two-pass covariance of each row's points, Jacobi eigen-decomposition; the
+    normal is the unit eigenvector of the smallest eigenvalue with its component of largest magnitude positive, or
+    (0,0,0) with ok = False where fewer than three neighbours are valid or they are collinear (l1 <= 1e-10 l2).
+    -> normals f32 [N,3][, eigenvalues f32 [N,3] ascending][, ok bool [N]]"""
+    n, k = check_point_normals_arguments(points, index)
+    points = _dev(points, torch.float32)
+    index = _dev(index, torch.int32)
+    dev = _same_device(points, index)
+    normals = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    eig = torch.empty((n, 3), dtype=torch.float32, device=dev) if return_eigenvalues else None
+    ok = torch.empty(n, dtype=torch.uint8, device=dev) if return_ok else None
+    context(dev).call("asr_hip_point_normals", ptr(points), i64(n), ptr(index), k, ptr(normals), ptr(eig), ptr(ok))
+    out = (normals,) + ((eig,) if return_eigenvalues else ()) + ((ok.bool(),) if return_ok else ())
+    return out if len(out) > 1 else normals
+
+
+def check_orient_arguments(points, normals, index, viewpoints):
+    """the shapes and ranges of orient_normals, or ValueError; no GPU involved -> (n, k, number of viewpoints)"""
+    shape = _shape(points)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError("points must have shape [N,3]")
+    n = shape[0]
+    if n >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 points")
+    if _shape(normals) != (n, 3):
+        raise ValueError("normals must have shape [N,3]")
+    k = 0
+    if index is not None:
+        ishape = _shape(index)
+        if len(ishape) != 2 or ishape[0] != n or ishape[1] < 1:
+            raise ValueError("index must have shape [N,k] with k >= 1")
+        k = ishape[1]
+    if viewpoints is None:
+        if index is None:
+            raise ValueError("give the neighbour lists (propagation) or viewpoints")
+        if n * k >= 2 ** 32:
+            raise ValueError("N k must be below 2^32")
+        return n, k, 0
+    vshape = _shape(viewpoints)
+    if vshape == (3,) or vshape == (1, 3):
+        return n, k, 1
+    if vshape == (n, 3):
+        return n, k, n
+    raise ValueError("viewpoints must have shape [3], [1,3] or [N,3]")
+
+
+def orient_normals(points, normals, index=None, viewpoints=None, return_flips=False, return_report=False):
+    """Consistent signs for unoriented normals (asr_hip_normals_orient; the contract is in include/asr_hip.h).
+    viewpoints [3] or [N,3]: every normal is turned towards its viewpoint.  viewpoints None: Hoppe's propagation along the
+    minimum spanning forest of the graph of `index` (int32 [N,k], -1 = no entry) under the weights 1 - |n_i . n_j|, each
+    tree signed so that its highest point looks up.  Points with a zero normal are skipped.
+    -> normals f32 [N,3][, flips bool [N]][, dict of ints: components, flipped, skipped, rounds]"""
+    n, k, nv = check_orient_arguments(points, normals, index, viewpoints)
+    points = _dev(points, torch.float32)
+    normals = _dev(normals, torch.float32)
+    index = _dev(index, torch.int32) if index is not None else None
+    if viewpoints is not None:
+        viewpoints = _dev(viewpoints, torch.float32).reshape(-1, 3)
+    dev = _same_device(points, normals, index, viewpoints)
+    out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    flips = torch.empty(n, dtype=torch.uint8, device=dev) if return_flips else None
+    report = (i64 * 4)()
+    context(dev).call("asr_hip_normals_orient", ptr(points), ptr(normals), i64(n), ptr(index), max(k, 1), ptr(viewpoints),
+                      i64(nv), ptr(out), ptr(flips), report)
+    res = (out,) + ((flips.bool(),) if return_flips else ())
+    if return_report:
+        res += (dict(zip(ORIENT_REPORT, (int(x) for x in report))),)
+    return res if len(res) > 1 else out
+
+
 def decode_mlp_at(code, shifts, w1, b1, w2, b2, w3, rows=None, voxel_sizes=None, gradient=False):
     """UNet5.decode(shifts, code[rows]) (net_definitions_torch.py:655-666) -> values [M,2]; with gradient=True
     (values, grad [M,3]) where grad is decode_with_gradient's d values[:,0] / d shift (:668-686, unscaled).

@@ -66,15 +66,18 @@ def _read_vertex_table(path):
     return data, types
 
 
-def read_points(path):
+def read_points(path, require_normals=True):
     """-> (points f32[N,3], normals f32[N,3], radii f32[N] or f32[0]).  ValueError if a required property is
-    missing (the reference returns empty arrays and then fails with "points is null!")."""
+    missing (the reference returns empty arrays and then fails with "points is null!").  require_normals=False: a file
+    without all of nx ny nz (a raw scan) is read too, and its normals are None."""
     data, _ = _read_vertex_table(path)
-    for req in ("x", "y", "z", "nx", "ny", "nz"):
+    have_normals = all(c in data for c in ("nx", "ny", "nz"))
+    for req in ("x", "y", "z") + (("nx", "ny", "nz") if require_normals else ()):
         if req not in data:
-            raise ValueError("%s: vertex property %s is missing (needed: x y z nx ny nz)" % (path, req))
+            raise ValueError("%s: vertex property %s is missing (needed: x y z%s)"
+                             % (path, req, " nx ny nz" if require_normals else ""))
     points = np.stack([data["x"], data["y"], data["z"]], 1).astype(np.float32)
-    normals = np.stack([data["nx"], data["ny"], data["nz"]], 1).astype(np.float32)
+    normals = np.stack([data["nx"], data["ny"], data["nz"]], 1).astype(np.float32) if have_normals else None
     radii = np.zeros(0, np.float32)
     for name in ("value", "radius"):  # main.cpp:103-106
         if name in data:

@@ -4,8 +4,9 @@ reference (cpp/bin/main.cpp:114-177: `asrtool --in point_cloud.ply --out mesh.pl
 
     python adaptive-surface-reconstruction_amd/asrtool.py --in scan.ply --out mesh.ply [--weights model.pt] [--precision NAME]
                                                           [--normals] [--colors] [--simplify K] [--smooth N] [--fill-holes N]
-                                                          [--thin SIZE]
+                                                          [--thin SIZE] [--estimate-normals K [--viewpoint x,y,z]]
     python adaptive-surface-reconstruction_amd/asrtool.py --thin-cloud scan.ply out.ply --cell SIZE
+    python adaptive-surface-reconstruction_amd/asrtool.py --orient-cloud raw.ply out.ply [--k K] [--viewpoint x,y,z]
     python adaptive-surface-reconstruction_amd/asrtool.py --compare mesh.ply reference.ply [--samples N] [--thresholds a,b,...] [--seed S]
     python adaptive-surface-reconstruction_amd/asrtool.py --decimate mesh.ply out.ply --cell SIZE
     python adaptive-surface-reconstruction_amd/asrtool.py --smooth-mesh mesh.ply out.ply [--iterations N] [--boundary free|pinned|along]
@@ -39,6 +40,14 @@ Options:
     --thin SIZE  Merges the input points inside one cell of a regular grid (and on one side of it: normals that point against
               each other stay apart) into their mean before anything else.  The cell used is the voxel size of the octree
               level around the cloud that is >= SIZE and < 2 SIZE.  Radii and colours are averaged with the points
+    --estimate-normals K  For scans without (oriented) normals: estimates them from the K nearest neighbours of each point
+              (3 <= K <= 64; PCA plane, signs propagated along the minimum spanning forest of the neighbour graph), after
+              --thin.  Normals in the file are then ignored; points without a usable estimate are dropped
+    --viewpoint x,y,z  --estimate-normals / --orient-cloud: turns every normal towards this position (the scanner's)
+              instead of propagating the signs
+    --orient-cloud IN.ply OUT.ply [--k K]  Instead of reconstructing: writes the cloud with normals estimated as
+              --estimate-normals K does (default 16), radii and colours carried over unchanged, points without a usable
+              estimate dropped; prints one JSON line with the report (components, flipped, skipped, rounds, points, dropped)
     --thin-cloud IN.ply OUT.ply --cell SIZE  Instead of reconstructing: writes the cloud merged as --thin SIZE does, with its
               normals and, where the input has them, radii and colours; prints the cell size used
     --fill-mesh MESH.ply OUT.ply --max-edges N  Instead of reconstructing: closes the holes of at most N edges of an existing
@@ -198,6 +207,69 @@ def _thin_cloud(argv):
     return 0
 
 
+def _normal_k(text):
+    """the K of --estimate-normals / --k, or None when it is no integer in 3..64"""
+    try:
+        k = int(text)
+    except (TypeError, ValueError):
+        return None
+    return k if 3 <= k <= 64 else None
+
+
+def _viewpoint(text):
+    """the x,y,z of --viewpoint as three finite floats, or None"""
+    try:
+        v = tuple(float(c) for c in text.split(","))
+    except (AttributeError, ValueError):
+        return None
+    return v if len(v) == 3 and all(abs(c) < float("inf") for c in v) else None
+
+
+def _orient_cloud(argv):
+    """--orient-cloud IN.ply OUT.ply [--k K] [--viewpoint x,y,z]: one JSON line, 0; a message on stderr and 1 (before any
+    GPU work) when something is wrong"""
+    import json
+    i = argv.index("--orient-cloud")
+    paths = argv[i + 1:i + 3]
+    if len(paths) < 2 or any(p.startswith("--") for p in paths):
+        sys.stderr.write("asrtool: --orient-cloud needs two files: IN.ply OUT.ply\n")
+        return 1
+    k = _normal_k(_option(argv, "--k")) if "--k" in argv else 16
+    if k is None:
+        sys.stderr.write("asrtool: --orient-cloud: --k takes a number of neighbours K, 3 <= K <= 64\n")
+        return 1
+    viewpoint = None
+    if "--viewpoint" in argv:
+        viewpoint = _viewpoint(_option(argv, "--viewpoint"))
+        if viewpoint is None:
+            sys.stderr.write("asrtool: --orient-cloud: --viewpoint takes three numbers x,y,z\n")
+            return 1
+    if not os.path.isfile(paths[0]):
+        sys.stderr.write("asrtool: --orient-cloud: no such file: %s\n" % paths[0])
+        return 1
+    from asr_hip import ply
+    import numpy as np
+    try:
+        points, _, radii = ply.read_points(paths[0], require_normals=False)
+        colors = ply.read_point_colors(paths[0])
+    except (ValueError, IndexError, OSError) as e:
+        sys.stderr.write("asrtool: --orient-cloud: cannot read %s as a point cloud: %s\n" % (paths[0], e))
+        return 1
+    if len(points) == 0:
+        sys.stderr.write("asrtool: --orient-cloud: %s has no points\n" % paths[0])
+        return 1
+    if not np.isfinite(points).all():
+        sys.stderr.write("asrtool: --orient-cloud: %s has points that are not finite\n" % paths[0])
+        return 1
+    import adaptivesurfacereconstruction as asr
+    est = asr.estimate_normals(points, k, viewpoint)
+    ok = est["ok"]
+    ply.write_points(paths[1], points[ok], est["normals"][ok], radii[ok] if len(radii) else None,
+                     colors=None if colors is None else colors[ok])
+    print(json.dumps(dict(est["report"], points=int(ok.sum()), dropped=int((~ok).sum()))))
+    return 0
+
+
 def _smooth_mesh(argv):
     """--smooth-mesh MESH.ply OUT.ply [--iterations N] [--boundary MODE]: 0, or a message on stderr and 1 (before any GPU
     work) when something is wrong"""
@@ -324,6 +396,8 @@ def main(argv=None):
         return _topology(argv)
     if "--thin-cloud" in argv:
         return _thin_cloud(argv)
+    if "--orient-cloud" in argv:
+        return _orient_cloud(argv)
     inp, out = _option(argv, "--in"), _option(argv, "--out")
     if inp is None or out is None:
         sys.stdout.write(HELP)
@@ -363,6 +437,17 @@ def main(argv=None):
         if thin is None:
             sys.stderr.write("asrtool: --thin takes a cell size SIZE, a positive number\n")
             return 1
+    normal_k, viewpoint = 0, None
+    if "--estimate-normals" in argv:  # before any GPU work
+        normal_k = _normal_k(_option(argv, "--estimate-normals"))
+        if normal_k is None:
+            sys.stderr.write("asrtool: --estimate-normals takes a number of neighbours K, 3 <= K <= 64\n")
+            return 1
+    if "--viewpoint" in argv:  # before any GPU work
+        viewpoint = _viewpoint(_option(argv, "--viewpoint"))
+        if viewpoint is None or not normal_k:
+            sys.stderr.write("asrtool: --viewpoint takes three numbers x,y,z and goes with --estimate-normals K\n")
+            return 1
     from asr_hip import ply
     colors = None
     if "--colors" in argv:  # before any GPU work: a cloud without colours is an error
@@ -372,7 +457,7 @@ def main(argv=None):
             return 1
     import adaptivesurfacereconstruction as asr
     print("reading points")
-    points, normals, radii = ply.read_points(inp)
+    points, normals, radii = ply.read_points(inp, require_normals=not normal_k)
     print("%d / %d" % (len(points), len(points)))
     extra = {} if colors is None else {"point_attributes": colors.astype("float32")}
     if simplify:
@@ -383,6 +468,10 @@ def main(argv=None):
         extra["fill_holes"] = fill_holes
     if thin:
         extra["thin"] = thin
+    if normal_k:
+        normals = None
+        extra["normal_k"] = normal_k
+        extra["viewpoint"] = viewpoint
     result = asr.reconstruct_surface(points, normals, radii, weights=_option(argv, "--weights"), precision=precision,
                                      vertex_normals="--normals" in argv, **extra)
     if colors is not None:

@@ -827,6 +827,40 @@ int asr_hip_points_merge_fill(asr_hip_context* ctx, float* points_out, float* no
     CTX_GUARD(ctx);
     return asr_points_merge_fill(ctx, points_out, normals_out, radii_out, attributes_out, counts_out, cluster_out);
 }
+int asr_hip_knn_index(asr_hip_context* ctx, const asr_octree_frame* frame, const float* points, int64_t n, int k,
+                      int32_t* index_out, float* sqdist_out) {
+    CTX_GUARD(ctx);
+    if (n < 1 || n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "knn_index: 1 <= n < 2^31 points are required");
+    if (k < 1 || k > 64) ASR_FAIL(ctx, ASR_HIP_EINVAL, "knn_index: k = %d is not in 1..64", k);
+    if (!frame || !points) ASR_FAIL(ctx, ASR_HIP_EINVAL, "knn_index: null argument");
+    ctx->scratch.reset();
+    return asr_geom_knn_index(ctx, frame, points, n, k, index_out, sqdist_out);
+}
+int asr_hip_point_normals(asr_hip_context* ctx, const float* points, int64_t n, const int32_t* index, int k,
+                          float* normals_out, float* eigenvalues_out, uint8_t* ok_out) {
+    CTX_GUARD(ctx);
+    if (n < 0 || n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "point_normals: 0 <= n < 2^31 points are required");
+    if (k < 3 || k > 64) ASR_FAIL(ctx, ASR_HIP_EINVAL, "point_normals: k = %d is not in 3..64", k);
+    if (n > 0 && (!points || !index || !normals_out)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "point_normals: null argument");
+    return asr_points_normals(ctx, points, n, index, k, normals_out, eigenvalues_out, ok_out);
+}
+int asr_hip_normals_orient(asr_hip_context* ctx, const float* points, const float* normals, int64_t n, const int32_t* index,
+                           int k, const float* viewpoints, int64_t num_viewpoints, float* normals_out, uint8_t* flips_out,
+                           int64_t report[4]) {
+    CTX_GUARD(ctx);
+    if (!report) ASR_FAIL(ctx, ASR_HIP_EINVAL, "normals_orient: null argument");
+    if (n < 0 || n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "normals_orient: 0 <= n < 2^31 points are required");
+    if (num_viewpoints != 0 && num_viewpoints != 1 && num_viewpoints != n)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "normals_orient: num_viewpoints must be 0, 1 or n");
+    if (n > 0 && (!points || !normals || !normals_out || (num_viewpoints > 0 && !viewpoints)))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "normals_orient: null argument");
+    if (num_viewpoints == 0) {
+        if (k < 1) ASR_FAIL(ctx, ASR_HIP_EINVAL, "normals_orient: k must be >= 1");
+        if (n > 0 && !index) ASR_FAIL(ctx, ASR_HIP_EINVAL, "normals_orient: propagation needs the neighbour lists");
+        if (n * (i64)k >= (i64(1) << 32)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "normals_orient: n k must be below 2^32");
+    }
+    return asr_points_orient(ctx, points, normals, n, index, k, viewpoints, num_viewpoints, normals_out, flips_out, report);
+}
 
 }  // extern "C"
 

@@ -507,6 +507,9 @@ int asr_geom_knn(asr_hip_context* ctx, const asr_octree_frame* frame, const floa
 // nearest point of each query among pts (exact, ties to the smallest index); either output may be null
 int asr_geom_nearest(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, const float* queries,
                      i64 m, int32_t* index_out, float* sqdist_out);
+// the k nearest points of every point, itself included, ordered by (squared distance, index); either output may be null
+int asr_geom_knn_index(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, int k,
+                       int32_t* index_out, float* sqdist_out);
 int asr_geom_dual_count(asr_hip_context* ctx, const u64* nodes, i64 num_nodes, const u64* leaves, i64 num_leaves,
                         i64* num_cells);
 int asr_geom_dual_fill(asr_hip_context* ctx, i64* out);
@@ -546,6 +549,12 @@ int asr_points_merge_count(asr_hip_context* ctx, const asr_octree_frame* frame, 
                            int level, int split_sides, i64* num_clusters, asr_points_merge_report* report);
 int asr_points_merge_fill(asr_hip_context* ctx, float* points_out, float* normals_out, float* radii_out,
                           float* attributes_out, int32_t* counts_out, int32_t* cluster_out);
+// PCA normals over given neighbour lists and their orientation (asr_hip_point_normals / asr_hip_normals_orient); arguments
+// validated by the callers
+int asr_points_normals(asr_hip_context* ctx, const float* points, i64 n, const int32_t* index, int k, float* normals_out,
+                       float* eigenvalues_out, uint8_t* ok_out);
+int asr_points_orient(asr_hip_context* ctx, const float* points, const float* normals, i64 n, const int32_t* index, int k,
+                      const float* viewpoints, i64 num_viewpoints, float* normals_out, uint8_t* flips_out, i64 report[4]);
 
 int asr_conv_agg_importance(asr_hip_context* ctx, const float* compat, const float* dist, i64 n,
                             float* out);

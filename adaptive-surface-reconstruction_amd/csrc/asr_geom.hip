@@ -1985,6 +1985,139 @@ __global__ __launch_bounds__(256) void k_nearest(asr_octree_frame f, const float
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Exact k-nearest-neighbour LISTS (asr_hip_knn_index): one wave per point in Morton order, the level walk of k_knn /
+// k_nearest.  The best 64 (squared distance bits << 32 | point index) keys seen on a level are one key per lane, ascending
+// over the lanes; row i of the output is the first k of them.  Candidates come 64 at a time: a batch in which no key lies
+// below the current k-th one (a ballot) is skipped, one with at most KNN_INSERT such keys has them inserted one by one,
+// any other is sorted by a bitonic network of lane shuffles, reversed and merged: min(best[l], batch[63 - l]) is a
+// bitonic sequence that holds the 64 smallest of the 128, six more compare-exchange steps sort it.  Keys are distinct (the index is part of them), so the order (d2, index) is total.
+// Acceptance of a level is k_nearest's with the k-th key in place of the best: every point outside the 3^3 block has a
+// COMPUTED squared distance of at least g^2 (g: the shrunk distance to the nearest inner face of the block), and the test
+// d2_k < g^2 is strict, so such a point cannot even tie with the k-th key -- no smaller index is lost at the block's
+// boundary.  A level that is not accepted hands its k-th key down as a bound (its block is a subset of the next one's),
+// and the list starts again, because the next block holds the same points once more.
+// ------------------------------------------------------------------------------------------
+__device__ inline u64 shfl_xor_u64(u64 v, int o) {
+    const u32 hi = __shfl_xor((u32)(v >> 32), o, 64), lo = __shfl_xor((u32)v, o, 64);
+    return ((u64)hi << 32) | lo;
+}
+__device__ inline u64 shfl_u64(u64 v, int src) {
+    const u32 hi = __shfl((u32)(v >> 32), src, 64), lo = __shfl((u32)v, src, 64);
+    return ((u64)hi << 32) | lo;
+}
+constexpr int KNN_INSERT = 12;  // survivors of a batch up to which they are inserted one by one instead of sorted and merged
+__global__ __launch_bounds__(256) void k_knn_index(asr_octree_frame f, const float4* __restrict__ sorted, i64 n, CellIndex ci,
+                                                   int lfine, int ldeep, int k, int32_t* __restrict__ index_out,
+                                                   float* __restrict__ sqdist_out) {
+    __shared__ int s_pref[4][28];
+    __shared__ int s_beg[4][28];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const i64 s = blockIdx.x * (i64)4 + wave;
+    if (s >= n) return;
+    const float4 me = sorted[s];
+    const u64 code = ci.codes[s];  // the point's level-21 cell as the index has it
+    const int cx = (int)asr_compact21(code), cy = (int)asr_compact21(code >> 1), cz = (int)asr_compact21(code >> 2);
+    const int kk = (int)(n < k ? n : k);
+    int lev0 = lfine;
+    if (ldeep > lfine) {  // crowded cells start deeper, as in k_knn
+        int b0, pop;
+        cell_range(ci, code >> (3 * (ASR_MAX_LEVEL - lfine)), lfine, b0, pop);
+        while (pop > KNN_CROWD && lev0 < ldeep) {
+            ++lev0;
+            cell_range(ci, code >> (3 * (ASR_MAX_LEVEL - lev0)), lev0, b0, pop);
+        }
+    }
+    u64 best = ~u64(0);   // lane l: the l-th smallest key of this level so far
+    u64 bound = ~u64(0);  // the k-th key of a finer level: no key of the answer is larger
+    for (int lev = lev0; lev >= 0; --lev) {
+        const int sh = ASR_MAX_LEVEL - lev, lim = (1 << lev) - 1;
+        const int x = cx >> sh, y = cy >> sh, z = cz >> sh;
+        int b = 0, cnt = 0;
+        if (lane < 27) {
+            const int xx = x + lane % 3 - 1, yy = y + (lane / 3) % 3 - 1, zz = z + lane / 9 - 1;
+            if (xx >= 0 && yy >= 0 && zz >= 0 && xx <= lim && yy <= lim && zz <= lim)
+                cell_range(ci, asr_morton3d((u64)xx, (u64)yy, (u64)zz), lev, b, cnt);
+        }
+        int pre = cnt;
+#pragma unroll
+        for (int o = 1; o < 32; o <<= 1) {
+            const int up = __shfl_up(pre, o, 64);
+            if (lane >= o) pre += up;
+        }
+        const int total = __shfl(pre, 26, 64);
+        if (total < kk && lev > 0) continue;  // (level 0 holds all n >= kk points)
+        __builtin_amdgcn_wave_barrier();
+        if (lane < 27) {
+            s_pref[wave][lane + 1] = pre;
+            s_beg[wave][lane] = b;
+        }
+        if (lane == 0) s_pref[wave][0] = 0;
+        __builtin_amdgcn_wave_barrier();
+        best = ~u64(0);
+        u64 worst = bound;  // min(bound, current k-th key): a candidate above it cannot enter the first k
+        for (int i0 = 0; i0 < total; i0 += 64) {
+            const int i = i0 + lane;
+            u64 key = ~u64(0);
+            if (i < total) {
+                const float4 pt = radius_candidate(sorted, s_pref[wave], s_beg[wave], i);
+                key = ((u64)__float_as_uint(sqdist3(pt.x, pt.y, pt.z, me.x, me.y, me.z)) << 32) |
+                      (u64)(u32)__float_as_int(pt.w);
+            }
+            if (key > worst) key = ~u64(0);
+            unsigned long long live = __ballot(key != ~u64(0));
+            if (!live) continue;
+            if (__popcll(live) <= KNN_INSERT) {
+                // few survivors (every batch but the first ones of a level): each is inserted where it belongs -- the keys
+                // below it are a prefix of the lanes, the rest moves up by one lane and the last key falls off
+                while (live) {
+                    const int src = __ffsll((long long)live) - 1;
+                    live &= live - 1;
+                    const u64 c = shfl_u64(key, src);
+                    if (c > worst) continue;  // (the k-th key has come down meanwhile)
+                    const int pos = __popcll(__ballot(best < c));
+                    const u32 uhi = __shfl_up((u32)(best >> 32), 1, 64), ulo = __shfl_up((u32)best, 1, 64);
+                    best = lane < pos ? best : (lane == pos ? c : (((u64)uhi << 32) | ulo));
+                    const u64 kth = shfl_u64(best, kk - 1);
+                    worst = kth < bound ? kth : bound;
+                }
+                continue;
+            }
+            // bitonic sort of the batch, ascending over the lanes
+#pragma unroll
+            for (int size = 2; size <= 64; size <<= 1) {
+#pragma unroll
+                for (int o = size >> 1; o > 0; o >>= 1) {
+                    const u64 other = shfl_xor_u64(key, o);
+                    const bool take_min = ((lane & o) == 0) == ((lane & size) == 0);
+                    key = take_min ? (other < key ? other : key) : (other > key ? other : key);
+                }
+            }
+            const u64 rev = shfl_u64(key, 63 - lane);
+            best = rev < best ? rev : best;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const u64 other = shfl_xor_u64(best, o);
+                best = (lane & o) == 0 ? (other < best ? other : best) : (other > best ? other : best);
+            }
+            const u64 kth = shfl_u64(best, kk - 1);
+            worst = kth < bound ? kth : bound;
+        }
+        if (lev == 0) break;
+        const u64 kth = shfl_u64(best, kk - 1);
+        const float g = fminf(fminf(nearest_face_gap(f, me.x, x, lev, f.offset[0]), nearest_face_gap(f, me.y, y, lev, f.offset[1])),
+                              nearest_face_gap(f, me.z, z, lev, f.offset[2]));
+        if (g > 0.f && kth != ~u64(0) && __uint_as_float((u32)(kth >> 32)) < g * g) break;
+        bound = kth < bound ? kth : bound;
+    }
+    if (lane < k) {
+        const i64 row = (i64)__float_as_int(me.w) * k + lane;
+        const bool have = lane < kk && best != ~u64(0);
+        if (index_out) index_out[row] = have ? (int32_t)(u32)best : -1;
+        if (sqdist_out) sqdist_out[row] = have ? __uint_as_float((u32)(best >> 32)) : __uint_as_float(0x7f800000u);
+    }
+}
+
 // rows are sorted by a segmented radix sort on (distance bits, index) keys; unpack + compat
 // ------------------------------------------------------------------------------------------
 // a11: CSR inversion
@@ -3472,6 +3605,28 @@ int asr_geom_nearest(asr_hip_context* ctx, const asr_octree_frame* frame, const 
                                       3 * (ASR_MAX_LEVEL - lfine))));
     k_nearest<<<grid_for(m, 4), BLK, 0, ctx->stream>>>(*frame, st.sorted, st.index(), lfine, ldeep, queries, qids, m,
                                                        index_out, sqdist_out);
+    ASR_CHECK_LAUNCH(ctx);
+    return ASR_HIP_OK;
+}
+
+// asr_hip_knn_index: the index of asr_geom_knn / asr_geom_nearest and one k_knn_index launch.  Host round trips: the cell
+// counts of the index build and the largest cell population; the search itself is enqueued and not waited for.
+int asr_geom_knn_index(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, int k,
+                       int32_t* index_out, float* sqdist_out) {
+    ASR_TRY(ensure_flags(ctx));
+    // One level finer than the radius search's index: knn_fine_level is about one point per cell of a cloud that fills the
+    // cube, a scanned SURFACE has dozens of points in its occupied cells there and a wave would walk a few hundred
+    // candidates per point; one level down it is a quarter.  Where that block holds fewer than k points (a cloud that does
+    // fill the cube) the walk moves up after the 27 look-ups.
+    const int lfine = std::min(ASR_MAX_LEVEL, knn_fine_level(n) + 1);
+    RadiusState st;
+    ASR_TRY(build_point_index_grown(ctx, frame, pts, n, 0, lfine, st, "knn index: cell table overflow"));
+    st.lhash = lfine;
+    int ldeep;
+    ASR_TRY(deepen_crowded_index(ctx, pts, st, lfine, &ldeep));
+    if (!index_out && !sqdist_out) return ASR_HIP_OK;  // (the points have been checked)
+    k_knn_index<<<grid_for(n, 4), BLK, 0, ctx->stream>>>(*frame, st.sorted, n, st.index(), lfine, ldeep, k, index_out,
+                                                         sqdist_out);
     ASR_CHECK_LAUNCH(ctx);
     return ASR_HIP_OK;
 }

@@ -42,6 +42,10 @@ enum Flag : int {
     F_MERGE_CLUSTERS = 25, // points merge: clusters (k_merge_starts) / ...
     F_MERGE_LARGEST = 26,  // ... members of the largest one / ...
     F_MERGE_LONG = 27,     // ... clusters longer than ASR_MERGE_LONG_CLUSTER (k_merge_stats)
+    F_ORIENT_SKIPPED = 28, // normal orientation: points with a zero normal (k_orient_init, k_orient_viewpoint)
+    F_ORIENT_FLIPPED = 29, // ... flipped normals (k_orient_flips, k_orient_viewpoint)
+    F_ORIENT_TREES = 30,   // ... trees of the spanning forest (k_orient_top)
+    F_ORIENT_HOOKED = 31,  // ... roots hooked in all rounds so far (k_orient_hook)
     F_COUNT
 };
 constexpr int FLAG_READ = 32;        // ints read_flags copies to the host

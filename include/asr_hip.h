@@ -694,6 +694,48 @@ int asr_hip_points_merge_count(asr_hip_context* ctx, const asr_octree_frame* fra
                                asr_points_merge_report* report);
 int asr_hip_points_merge_fill(asr_hip_context* ctx, float* points_out_dev, float* normals_out_dev, float* radii_out_dev,
                               float* attributes_out_dev, int32_t* counts_out_dev, int32_t* cluster_out_dev);
+
+/* ---- oriented normals for clouds without them (not in the reference) ---------------------------------- */
+/* Exact k-nearest-neighbour lists.  With d2(i, j) = ((px-qx)^2 + (py-qy)^2) + (pz-qz)^2 in f32 without contraction (the
+ * arithmetic of asr_hip_nearest_point), row i of index_out_dev (int32 [n,k]) and sqdist_out_dev (f32 [n,k]) holds the k
+ * smallest pairs (d2(i, j), j) in lexicographic order, ascending: the point itself is included, ties in distance go to the
+ * smaller index -- the result of a brute-force search, for duplicated points and lattices too.  1 <= k <= 64 and
+ * 1 <= n < 2^31, else ASR_HIP_EINVAL; rows of a cloud with n < k are padded with index -1 and distance +inf.  Non-finite
+ * points are ASR_HIP_EINVAL.  The frame only defines the acceleration grid and must contain the points, as for
+ * asr_hip_knn_radius.  Either output may be NULL.  Plain stores: the same inputs give the same bits.  The index build
+ * reads its cell counts back; the search itself is not waited for. */
+int asr_hip_knn_index(asr_hip_context* ctx, const asr_octree_frame* frame, const float* points_dev, int64_t n, int k,
+                      int32_t* index_out_dev, float* sqdist_out_dev);
+/* PCA normals over given lists (from asr_hip_knn_index or hand-made): index_dev int32 [n,k], 3 <= k <= 64; entries equal
+ * to -1 are skipped, any other entry outside [0, n) is ASR_HIP_EINVAL (checked on the device).  Per point, all in f64 from
+ * the f32 coordinates, in slot order (the same bits on every run): the mean of the m valid neighbours, then the six
+ * centred sums divided by m (two passes); the symmetric 3 x 3 is diagonalised by cyclic Jacobi sweeps until its
+ * off-diagonal elements are exactly zero.  eigenvalues_out_dev (f32 [n,3], may be NULL): the eigenvalues ascending,
+ * negative rounding residues clamped to 0.  normals_out_dev (f32 [n,3]): the unit eigenvector of the smallest, rounded to
+ * f32 and signed so that its component of largest magnitude is positive (ties: the lowest axis) -- a function of the list
+ * alone.  ok_out_dev (u8 [n], may be NULL): 0, with the normal (0,0,0), when m < 3 or l1 <= 1e-10 l2 (coincident or
+ * collinear neighbours, l2 == 0 included), else 1.  One launch, one read-back (the index check). */
+int asr_hip_point_normals(asr_hip_context* ctx, const float* points_dev, int64_t n, const int32_t* index_dev, int k,
+                          float* normals_out_dev, float* eigenvalues_out_dev, uint8_t* ok_out_dev);
+/* Consistent signs.  report = {components, flipped, skipped, rounds}.  Points with a zero normal are skipped: never
+ * flipped, members of no component, counted in `skipped`.  normals_out_dev (f32 [n,3]) may be normals_dev; flips_out_dev
+ * (u8 [n], 1 = negated) may be NULL.
+ * num_viewpoints 1 or n (viewpoints_dev f32 [1,3] or [n,3]): flip iff (nx (vx-px) + ny (vy-py)) + nz (vz-pz) < 0 in f32
+ *   without contraction; index_dev may be NULL; components and rounds are 0.
+ * num_viewpoints 0: Hoppe's propagation over the minimum spanning forest of the k-NN graph.
+ *   Edges: every directed slot e = i k + s with j = index[i,s], j != i, j >= 0 and both normals non-zero, read as the
+ *     undirected edge {i, j}; entries outside [0, n) other than -1 are ASR_HIP_EINVAL.  Weight w = max(0, 1 - |dot|) with
+ *     dot = (nx_i nx_j + ny_i ny_j) + nz_i nz_j in f32 without contraction (bitwise symmetric); key = bits(w) << 32 | e,
+ *     which needs n k < 2^32 (else ASR_HIP_EINVAL).  The keys are distinct, so the minimum spanning forest under them is
+ *     unique.  A forest edge asks for opposite flips of its ends iff dot < 0; that fixes every sign relative to its tree.
+ *   Each tree's sign: its member with the largest z (ties: the smallest index; -0 == +0) gets n_z >= 0; n_z == 0 there
+ *     leaves the tree as propagated.
+ *   Built by Boruvka rounds over a signed union-find (64-bit atomicMin per root, of a mutual pair the smaller root stays),
+ *   flattened without read-write races: the result does not depend on scheduling.  One read-back per round; rounds = the
+ *   rounds that hooked a root, at most ceil(log2 n) + 1. */
+int asr_hip_normals_orient(asr_hip_context* ctx, const float* points_dev, const float* normals_dev, int64_t n,
+                           const int32_t* index_dev, int k, const float* viewpoints_dev, int64_t num_viewpoints,
+                           float* normals_out_dev, uint8_t* flips_out_dev, int64_t report[4]);
 /* (asr_hip_implicit_query, the whole-path query on the last forward, is declared after asr_hip_implicit_stage_ms) */
 
 /* ---- whole path: the section of asr::ReconstructSurface between the pre-filter and the
