@@ -809,7 +809,7 @@ int asr_hip_points_merge_count(asr_hip_context* ctx, const asr_octree_frame* fra
                                const int8_t* levels, int level, int split_sides, int64_t* num_clusters_out,
                                asr_points_merge_report* report) {
     CTX_GUARD(ctx);
-    ctx->merge = AsrMergeState();
+    pending_begin(ctx->pending);  // a count refused for its arguments leaves nothing to fill either
     if (!frame || !num_clusters_out || (n > 0 && !points)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "points_merge_count: null argument");
     if (n < 0 || n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "points_merge_count: 0 <= n < 2^31 points are required");
     if (!levels && (level < 0 || level > ASR_MAX_LEVEL))

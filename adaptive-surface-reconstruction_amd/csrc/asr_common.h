@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/asr_hip.h"
+#include "asr_pending.h"
 
 typedef uint64_t u64;
 typedef int64_t i64;
@@ -27,6 +28,7 @@ struct Arena {
     std::vector<Slab> slabs;
     size_t min_slab = size_t(256) << 20;
     size_t cap = 0;  // option "arena_cap_mb": the arena never reserves more than this many bytes (0: no limit)
+    uint64_t generation = 0;  // resets and rewinds so far: older pointers may have been handed out again (asr_pending.h)
 
     void* alloc(size_t bytes) {
         bytes = (bytes + 255) & ~size_t(255);
@@ -46,6 +48,7 @@ struct Arena {
     }
     void reset() {
         for (auto& s : slabs) s.used = 0;
+        ++generation;
     }
     size_t reserved() const {
         size_t t = 0;
@@ -68,6 +71,7 @@ static inline void arena_mark(const Arena& a, ArenaMark& m) {
 }
 static inline void arena_rewind(Arena& a, const ArenaMark& m) {
     for (size_t i = 0; i < a.slabs.size(); ++i) a.slabs[i].used = i < m.used.size() ? m.used[i] : 0;
+    ++a.generation;
 }
 
 struct GridDev {
@@ -176,7 +180,6 @@ struct AsrPointIndex {
 
 // asr_hip_points_merge_count -> _fill: the caller's inputs and the sorted member lists in the scratch arena
 struct AsrMergeState {
-    bool valid = false;
     const float *points = nullptr, *normals = nullptr, *radii = nullptr, *attributes = nullptr;
     int channels = 0;
     i64 n = 0, clusters = 0, num_long = 0;
@@ -254,9 +257,10 @@ struct asr_hip_context {
     size_t split_part_bytes = 0;
     unsigned* d_status = nullptr;  // sharded forward: the status word of asr_shard_agree
     unsigned* d_absmax = nullptr;  // f16x2: running maxima of the network's activation buffers; [255]: one-off inputs
-    void* radius_state = nullptr;  // RadiusState of asr_geom.hip (between _count and _fill)
-    void* mesh_state = nullptr;    // MeshState of asr_mesh.hip (between _count and _fill)
-    AsrMergeState merge;           // asr_points.hip (between _count and _fill)
+    Pending pending;               // which _count may be filled, under which generation of `scratch` (asr_pending.h)
+    void* geom_state = nullptr;    // what that count parked: GeomState of asr_geom.hip (radius search, dual cells),
+    void* mesh_state = nullptr;    // MeshState of asr_mesh.hip (contour, components, simplify, edge table, fill holes),
+    AsrMergeState merge;           // asr_points.hip.  The auxiliary context has a slot and states of its own.
     std::map<std::string, std::pair<const void*, size_t>> named;  // asr_hip_implicit_get
     int device = 0;                 // HIP device of this context (helper threads must select it)
     asr_hip_context* aux = nullptr;  // second stream + arenas: the aggregation search runs there, overlapped

@@ -3050,9 +3050,8 @@ int asr_geom_voxel_info(asr_hip_context* ctx, const asr_octree_frame* frame, con
     return ASR_HIP_OK;
 }
 
-// state kept in the scratch arena between _count and _fill
+// the point index of a search; the context's own (rstate) is what asr_geom_radius_count parks for asr_geom_radius_fill
 struct RadiusState {
-    bool valid = false;
     asr_octree_frame frame;
     float4* sorted = nullptr;  // points in Morton order, w = original index
     int32_t* ids = nullptr;    // original index of the point at each Morton position
@@ -3074,8 +3073,6 @@ struct RadiusState {
     i64 num_heavy = 0;
     int* hc_pref = nullptr;    // cell ranges of the heavy rows (k_radius_heavy_cells)
     int* hc_beg = nullptr;
-    const u64* dual_leaves = nullptr;  // leaf array of the pending dual-cell count / fill pair
-    i64 dual_nl = 0;
     float* srad = nullptr;     // radii in Morton order (when the count call was given them)
     const float* radii_src = nullptr;
     int lsort = 0;             // the points are sorted on the code bits down to this level
@@ -3084,13 +3081,24 @@ struct RadiusState {
     bool aligned_main = false; // ... in the per-voxel kernel as well (option search_half = 2)
     AlignedQ aq = {nullptr, nullptr, nullptr, -1};
 };
-static RadiusState& rstate(asr_hip_context* ctx) {
-    if (!ctx->radius_state) ctx->radius_state = new RadiusState();
-    return *(RadiusState*)ctx->radius_state;
+struct DualState {  // what asr_geom_dual_count parks for asr_geom_dual_fill
+    HashTab tab;                   // node key -> leaf index, -1 for an inner node
+    const i64* offsets = nullptr;  // exclusive scan of the cells per leaf (nl + 1)
+    const u64* leaves = nullptr;   // the caller's leaf array
+    i64 nl = 0;
+};
+struct GeomState {
+    RadiusState radius;  // also the home of the sticky cell_grow
+    DualState dual;
+};
+static GeomState& gstate(asr_hip_context* ctx) {
+    if (!ctx->geom_state) ctx->geom_state = new GeomState();
+    return *(GeomState*)ctx->geom_state;
 }
+static RadiusState& rstate(asr_hip_context* ctx) { return gstate(ctx).radius; }
 void asr_geom_release(asr_hip_context* ctx) {
-    delete (RadiusState*)ctx->radius_state;
-    ctx->radius_state = nullptr;
+    delete (GeomState*)ctx->geom_state;
+    ctx->geom_state = nullptr;
 }
 
 // points sorted by level-21 Morton code (sort_points) + hash map (cell, level) -> [start, end) for levels
@@ -3310,17 +3318,17 @@ int asr_geom_radius_count(asr_hip_context* ctx, const asr_octree_frame* frame, c
                           i64 n, const float* centers, const float* sizes, i64 v, i64* rs,
                           i64* num_pairs, Arena* keep, const float* radii, const u64* voxel_keys, int lmin_hint,
                           int lmax_hint, const AsrPointIndex* pre) {
+    pending_begin(ctx->pending);  // (the caller has recycled the scratch arena, or shares it with this search)
     ASR_TRY(ensure_flags(ctx));
     RadiusState& st = rstate(ctx);
-    st.valid = false;
+    st.n = n, st.v = v;  // what the fill call must name again
     if (v <= 0) {
         *num_pairs = 0;
         if (rs) ASR_HIP_CHECK(ctx, hipMemsetAsync(rs, 0, sizeof(i64), ctx->stream));
-        return ASR_HIP_OK;
+        return count_done(ctx, PendingOp::MultiRadiusSearch);
     }
     if (n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "too many points for int32 indices");
     HostFlags host;
-    st.v = v;
     int lmin = lmin_hint, lmax = lmax_hint;
     if (lmin < 0 || lmax < lmin) ASR_TRY(query_level_range(ctx, frame, sizes, v, &lmin, &lmax));
     // aligned queries (voxel_keys): half-size cells of level L + 1 for the voxel levels L <= lhalf_max (see AlignedQ)
@@ -3427,8 +3435,7 @@ int asr_geom_radius_count(asr_hip_context* ctx, const asr_octree_frame* frame, c
     }
     ASR_TRY(scan_counts(ctx, ctx->scratch, counts, rs, v + 1));
     ASR_TRY(read_i64(ctx, rs + v, num_pairs));
-    st.valid = true;
-    return ASR_HIP_OK;
+    return count_done(ctx, PendingOp::MultiRadiusSearch);
 }
 
 // KDTree::ComputeRadiusNeighbors (cpp/lib/nsearch.cpp:88-105): per point the number of points with
@@ -3637,10 +3644,10 @@ int asr_geom_radius_fill(asr_hip_context* ctx, const float* pts, const float* ra
     RadiusState& st = rstate(ctx);
     (void)pts;
     if (sorted_out) *sorted_out = nullptr;
-    if (v <= 0) return ASR_HIP_OK;
-    if (!st.valid || st.n != n || st.v != v)
+    if (!fill_begin(ctx, PendingOp::MultiRadiusSearch) || st.n != n || st.v != v)
         ASR_FAIL(ctx, ASR_HIP_EINVAL,
                  "asr_hip_multi_radius_search_fill must follow the matching _count call");
+    if (v <= 0) return ASR_HIP_OK;
     if (sorted_out) *sorted_out = st.sorted;
     float* srad = st.srad;  // gathered with the points when the count call had the radii
     if (compat && !srad) {
@@ -3706,25 +3713,23 @@ int asr_geom_radius_fill(asr_hip_context* ctx, const float* pts, const float* ra
                                                                         radii, st.rank, idx, spos, dist, compat, idx_bits);
         ASR_CHECK_LAUNCH(ctx);
     }
-    st.valid = false;
     return ASR_HIP_OK;
 }
 
 // Dual cells of the LAST octree build (ctx->nodes / ctx->leaves).  count: number of cells; fill:
 // [D,8] leaf indices, leaf order x corner order.
 int asr_geom_dual_count(asr_hip_context* ctx, const u64* nodes, i64 nn, const u64* leaves, i64 nl, i64* num_cells) {
-    ASR_TRY(ensure_flags(ctx));
+    ASR_TRY(count_begin(ctx));
     *num_cells = 0;
-    RadiusState& st0 = rstate(ctx);
-    st0.dual_leaves = leaves;
-    st0.dual_nl = nl;
-    if (nl <= 0) return ASR_HIP_OK;
-    ctx->scratch.reset();
+    DualState& st = gstate(ctx).dual;
+    st = DualState();
+    st.leaves = leaves;
+    st.nl = nl;
+    if (nl <= 0) return count_done(ctx, PendingOp::DualCells);
     HashTab t;
     u64 cap = next_pow2((u64)std::max<i64>(1024, 2 * nn));
     ASR_TRY(make_table(ctx, ctx->scratch, cap, true, t));
     ASR_HIP_CHECK(ctx, hipMemsetAsync(t.vals, 0xFF, cap * sizeof(int32_t), ctx->stream));  // -1 = inner
-    ASR_TRY(fresh_flags(ctx));
     int32_t* keep = t.vals;
     t.vals = arena_alloc<int32_t>(ctx->scratch, cap);  // throw-away values for the node pass
     if (!t.vals) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
@@ -3740,25 +3745,20 @@ int asr_geom_dual_count(asr_hip_context* ctx, const u64* nodes, i64 nn, const u6
     ASR_CHECK_LAUNCH(ctx);
     ASR_TRY(scan_counts(ctx, ctx->scratch, counts, offsets, nl + 1));
     ASR_TRY(read_i64(ctx, offsets + nl, num_cells));
-    RadiusState& st = rstate(ctx);  // park the table + offsets for the fill call
-    st.valid = false;
     st.tab = t;
-    st.start = (int32_t*)offsets;
-    st.v = -nl;  // marks "dual state"
-    return ASR_HIP_OK;
+    st.offsets = offsets;
+    return count_done(ctx, PendingOp::DualCells);
 }
 int asr_geom_dual_fill(asr_hip_context* ctx, i64* out) {
-    RadiusState& st = rstate(ctx);
-    const i64 nl = st.dual_nl;
-    if (nl <= 0) return ASR_HIP_OK;
-    if (st.v != -nl) ASR_FAIL(ctx, ASR_HIP_EINVAL, "dual_fill must follow the matching dual_count call");
+    if (!fill_begin(ctx, PendingOp::DualCells))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "dual_fill must follow the matching dual_count call");
+    const DualState& st = gstate(ctx).dual;
+    if (st.nl <= 0) return ASR_HIP_OK;
     HostFlags host;
-    k_dual_fill<<<grid_for(nl, BLK), BLK, 0, ctx->stream>>>(st.dual_leaves, nl, st.tab, (const i64*)st.start, out,
-                                                            ctx->d_flags);
+    k_dual_fill<<<grid_for(st.nl, BLK), BLK, 0, ctx->stream>>>(st.leaves, st.nl, st.tab, st.offsets, out, ctx->d_flags);
     ASR_CHECK_LAUNCH(ctx);
     ASR_TRY(read_flags(ctx, host));
-    st.v = 0;
-    // (F_OVERFLOW: the node map of the _count call lost a key -- the same block when nothing ran in between)
+    // (F_OVERFLOW: the node map of the _count call lost a key -- the same block when nothing took fresh flags in between)
     if (host[F_DUAL_KEY] || host[F_OVERFLOW]) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "invalid key after searching for node (cpp/lib/grid.cpp:435-440)");
     return ASR_HIP_OK;
 }

@@ -28,12 +28,12 @@ __constant__ int c_cube_faces[6][4] = {{0, 1, 3, 2}, {4, 6, 7, 5}, {1, 5, 7, 3},
                                        {2, 3, 7, 6}, {0, 2, 6, 4}, {0, 4, 5, 1}};
 __constant__ int c_owned_edges[3][2] = {{0, 1}, {1, 3}, {1, 5}};  // edge subset {0,1,9}
 
-struct MeshState {
-    int kind = 0;  // 1 = contour, 2 = components, 3 = simplify, 4 = edge table, 5 = fill holes
-    // contour
+// What each _count call parks for its _fill: the caller's inputs and arrays in the scratch arena.  Which of them is live
+// is ctx->pending's business (asr_pending.h), never a field's.
+struct ContourState {
     const float* values = nullptr;
     const i64* duals = nullptr;
-    i64 num_values = 0, num_duals = 0, num_active = 0, num_extra = 0, num_tri = 0;
+    i64 num_active = 0, num_extra = 0, num_tri = 0;
     float thr = 0;
     int32_t* active = nullptr;  // vertex -> dual
     float* vtx = nullptr;       // [num_active,3]
@@ -41,32 +41,49 @@ struct MeshState {
     int32_t* adj = nullptr;
     i64* tri_off = nullptr;  // per (vertex, owned edge)
     i64* extra_off = nullptr;
-    // components
+};
+struct ComponentsState {
     const float* in_vtx = nullptr;
     const int32_t* in_tri = nullptr;
     i64 nv = 0, nt = 0, nv_out = 0, nt_out = 0;
     i64* v_off = nullptr;  // exclusive scan of the vertex keep flags (nv+1)
     i64* t_off = nullptr;  // same for triangles
-    // simplify (in_tri, nv, nt, nv_out, nt_out, t_off as above)
-    i64 nc = 0;                       // clusters
+};
+struct SimplifyState {
+    const int32_t* in_tri = nullptr;
+    i64 nv = 0, nt = 0, nv_out = 0, nt_out = 0;
+    i64 nc = 0;                        // clusters
     const int32_t* cluster = nullptr;  // vertex -> cluster
-    const float* cpos = nullptr;      // [nc,3] position of every cluster
-    i64* c_off = nullptr;             // exclusive scan of the clusters a surviving triangle references (nc+1)
-    // edge table
+    const float* cpos = nullptr;       // [nc,3] position of every cluster
+    i64* c_off = nullptr;              // exclusive scan of the clusters a surviving triangle references (nc+1)
+    i64* t_off = nullptr;              // exclusive scan of the surviving triangles (nt+1)
+};
+struct EdgesState {
     i64 num_edges = 0;
-    const u64* e_keys = nullptr;   // sorted side keys
-    const i64* e_start = nullptr;  // first side of every edge (num_edges+1)
-    const i64* e_count = nullptr;  // the number of edges, on the device
-    // fill holes (in_vtx, in_tri, nv, nt as above; nv_out - nv hubs, nt_out - nt new triangles)
-    i64 f_rim_vertices = 0, f_long = 0;  // vertices on filled rims; filled rims longer than FILL_CUT
-    const u64* f_keys = nullptr;         // (rim id << 32) | vertex of the vertices on filled rims, sorted
-    const int* f_len = nullptr;          // per rim id: its number of boundary edges
-    const int* f_succ = nullptr;         // tail -> head of the boundary edge that leaves a vertex
-    const int* f_start = nullptr;        // per filled rim id: its first entry in f_keys
-    const i64* f_hub_off = nullptr;      // exclusive scan over the rim ids: hubs (nv+1)
-    const i64* f_tri_off = nullptr;      // the same for the new triangles
-    const int32_t* f_hub_rims = nullptr;   // hub -> rim id
-    const int32_t* f_long_rims = nullptr;  // the filled rims a whole wave sums
+    const u64* keys = nullptr;   // sorted side keys
+    const i64* start = nullptr;  // first side of every edge (num_edges+1)
+    const i64* count = nullptr;  // the number of edges, on the device
+};
+struct FillHolesState {  // nv_out - nv hubs, nt_out - nt new triangles
+    const float* in_vtx = nullptr;
+    const int32_t* in_tri = nullptr;
+    i64 nv = 0, nt = 0, nv_out = 0, nt_out = 0;
+    i64 rim_vertices = 0, num_long = 0;  // vertices on filled rims; filled rims longer than FILL_CUT
+    const u64* keys = nullptr;           // (rim id << 32) | vertex of the vertices on filled rims, sorted
+    const int* len = nullptr;            // per rim id: its number of boundary edges
+    const int* succ = nullptr;           // tail -> head of the boundary edge that leaves a vertex
+    const int* start = nullptr;          // per filled rim id: its first entry in keys
+    const i64* hub_off = nullptr;        // exclusive scan over the rim ids: hubs (nv+1)
+    const i64* tri_off = nullptr;        // the same for the new triangles
+    const int32_t* hub_rims = nullptr;   // hub -> rim id
+    const int32_t* long_rims = nullptr;  // the filled rims a whole wave sums
+};
+struct MeshState {
+    ContourState contour;
+    ComponentsState components;
+    SimplifyState simplify;
+    EdgesState edges;
+    FillHolesState fill_holes;
 };
 
 __device__ inline bool crossing(const float* values, float thr, i64 a, i64 b) {  // :81-111
@@ -1149,11 +1166,6 @@ MeshState& mstate(asr_hip_context* ctx) {
     if (!ctx->mesh_state) ctx->mesh_state = new MeshState();
     return *(MeshState*)ctx->mesh_state;
 }
-
-#define MESH_ALLOC(var, T, count)                                                    \
-    T* var = arena_alloc<T>(ctx->scratch, (size_t)(count));                          \
-    if (!var) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed")
-
 }  // namespace
 
 void asr_mesh_release(asr_hip_context* ctx) {
@@ -1164,24 +1176,19 @@ void asr_mesh_release(asr_hip_context* ctx) {
 int asr_mesh_contour_count(asr_hip_context* ctx, const float* values, i64 num_values, const i64* duals,
                            i64 num_duals, const float* positions, float threshold, i64* num_vertices,
                            i64* num_triangles) {
-    MeshState& st = mstate(ctx);
-    st = MeshState();
+    ASR_TRY(count_begin(ctx));
+    ContourState& st = mstate(ctx).contour;
+    st = ContourState();
     *num_vertices = 0;
     *num_triangles = 0;
-    if (num_duals <= 0 || num_values <= 0) {
-        st.kind = 1;
-        return ASR_HIP_OK;
-    }
+    if (num_duals <= 0 || num_values <= 0) return count_done(ctx, PendingOp::Contour);
     if (num_values >= (i64(1) << 31) || num_duals >= (i64(1) << 31))
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "contour: more than 2^31 voxels or dual cells");
-    ASR_TRY(ensure_flags(ctx));
-    ctx->scratch.reset();
     hipStream_t s = ctx->stream;
-    ASR_TRY(fresh_flags(ctx));
-    MESH_ALLOC(flag, i64, num_duals + 1);
-    MESH_ALLOC(npairs, i64, num_duals + 1);
-    MESH_ALLOC(voff, i64, num_duals + 1);
-    MESH_ALLOC(poff, i64, num_duals + 1);
+    SCRATCH_ALLOC(flag, i64, num_duals + 1);
+    SCRATCH_ALLOC(npairs, i64, num_duals + 1);
+    SCRATCH_ALLOC(voff, i64, num_duals + 1);
+    SCRATCH_ALLOC(poff, i64, num_duals + 1);
     k_contour_active<<<grid_for(num_duals + 1, BLK), BLK, 0, s>>>(values, num_values, duals, num_duals, threshold,
                                                                    flag, npairs, ctx->d_flags);
     ASR_CHECK_LAUNCH(ctx);
@@ -1195,25 +1202,20 @@ int asr_mesh_contour_count(asr_hip_context* ctx, const float* values, i64 num_va
     if (host[F_BAD_INDEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "contour: dual vertex index out of range");
     st.values = values;
     st.duals = duals;
-    st.num_values = num_values;
-    st.num_duals = num_duals;
     st.thr = threshold;
     st.num_active = na;
-    if (na == 0) {
-        st.kind = 1;
-        return ASR_HIP_OK;
-    }
-    MESH_ALLOC(active, int32_t, na);
-    MESH_ALLOC(pairs, u64, np);
-    MESH_ALLOC(pairs_sorted, u64, np);
-    MESH_ALLOC(adj_rs, i64, num_values + 1);
-    MESH_ALLOC(adj, int32_t, np);
-    MESH_ALLOC(tri_cnt, i64, na * 3 + 1);
-    MESH_ALLOC(extra_cnt, i64, na * 3 + 1);
-    MESH_ALLOC(tri_off, i64, na * 3 + 1);
-    MESH_ALLOC(extra_off, i64, na * 3 + 1);
+    if (na == 0) return count_done(ctx, PendingOp::Contour);
+    SCRATCH_ALLOC(active, int32_t, na);
+    SCRATCH_ALLOC(pairs, u64, np);
+    SCRATCH_ALLOC(pairs_sorted, u64, np);
+    SCRATCH_ALLOC(adj_rs, i64, num_values + 1);
+    SCRATCH_ALLOC(adj, int32_t, np);
+    SCRATCH_ALLOC(tri_cnt, i64, na * 3 + 1);
+    SCRATCH_ALLOC(extra_cnt, i64, na * 3 + 1);
+    SCRATCH_ALLOC(tri_off, i64, na * 3 + 1);
+    SCRATCH_ALLOC(extra_off, i64, na * 3 + 1);
     // vertices: room for one fan centre per (dual, edge) is far too much; sized after the count
-    MESH_ALLOC(vtx0, float, na * 3);
+    SCRATCH_ALLOC(vtx0, float, na * 3);
     k_contour_vertices<<<grid_for(num_duals, BLK), BLK, 0, s>>>(values, duals, num_duals, positions, threshold,
                                                                 voff, poff, active, vtx0, pairs);
     ASR_CHECK_LAUNCH(ctx);
@@ -1235,7 +1237,6 @@ int asr_mesh_contour_count(asr_hip_context* ctx, const float* values, i64 num_va
         ASR_FAIL(ctx, ASR_HIP_ELOGIC, "contour: more than %d dual cells around one edge", ASR_USET_CAP);
     if (na + st.num_extra >= (i64(1) << 31) || st.num_tri >= (i64(1) << 31) / 3)
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "contour: mesh does not fit 32-bit indices");
-    st.kind = 1;  // only a count that succeeded may be filled
     st.active = active;
     st.vtx = vtx0;
     st.adj_rs = adj_rs;
@@ -1244,13 +1245,13 @@ int asr_mesh_contour_count(asr_hip_context* ctx, const float* values, i64 num_va
     st.extra_off = extra_off;
     *num_vertices = na + st.num_extra;
     *num_triangles = st.num_tri;
-    return ASR_HIP_OK;
+    return count_done(ctx, PendingOp::Contour);  // only a count that succeeded may be filled
 }
 
 int asr_mesh_contour_fill(asr_hip_context* ctx, float* vertices, int32_t* triangles) {
-    MeshState& st = mstate(ctx);
-    if (st.kind != 1) ASR_FAIL(ctx, ASR_HIP_EINVAL, "contour_fill must follow the matching contour_count call");
-    st.kind = 0;
+    if (!fill_begin(ctx, PendingOp::Contour))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "contour_fill must follow the matching contour_count call");
+    const ContourState& st = mstate(ctx).contour;
     const i64 na = st.num_active;
     if (na == 0) return ASR_HIP_OK;
     hipStream_t s = ctx->stream;
@@ -1267,22 +1268,19 @@ int asr_mesh_contour_fill(asr_hip_context* ctx, float* vertices, int32_t* triang
 
 int asr_mesh_components_count(asr_hip_context* ctx, const float* vertices, i64 nv, const int32_t* triangles,
                               i64 nt, i64 keep_n, i64 min_size, i64* nv_out, i64* nt_out) {
-    MeshState& st = mstate(ctx);
-    st = MeshState();
-    st.kind = 2;
+    ASR_TRY(count_begin(ctx));
+    ComponentsState& st = mstate(ctx).components;
+    st = ComponentsState();
     *nv_out = 0;
     *nt_out = 0;
-    if (nv <= 0) return ASR_HIP_OK;
+    if (nv <= 0) return count_done(ctx, PendingOp::Components);
     if (nv >= (i64(1) << 31) || nt >= (i64(1) << 31) / 3)
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "components: mesh does not fit 32-bit indices");
-    ASR_TRY(ensure_flags(ctx));
-    ctx->scratch.reset();
     hipStream_t s = ctx->stream;
-    ASR_TRY(fresh_flags(ctx));
-    MESH_ALLOC(parent, int, nv);
-    MESH_ALLOC(is_root, i64, nv + 1);
-    MESH_ALLOC(label, i64, nv + 1);
-    MESH_ALLOC(comp, int32_t, nv);
+    SCRATCH_ALLOC(parent, int, nv);
+    SCRATCH_ALLOC(is_root, i64, nv + 1);
+    SCRATCH_ALLOC(label, i64, nv + 1);
+    SCRATCH_ALLOC(comp, int32_t, nv);
     k_uf_init<<<grid_for(nv, BLK), BLK, 0, s>>>(parent, nv);
     ASR_CHECK_LAUNCH(ctx);
     if (nt > 0) {
@@ -1297,10 +1295,10 @@ int asr_mesh_components_count(asr_hip_context* ctx, const float* vertices, i64 n
     HostFlags host;
     ASR_TRY(read_flags(ctx, host));
     if (host[F_BAD_INDEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "components: triangle index out of range");
-    MESH_ALLOC(sizes, int, nc);
-    MESH_ALLOC(keys, u64, nc);
-    MESH_ALLOC(keys_sorted, u64, nc);
-    MESH_ALLOC(keep, uint8_t, nc);
+    SCRATCH_ALLOC(sizes, int, nc);
+    SCRATCH_ALLOC(keys, u64, nc);
+    SCRATCH_ALLOC(keys_sorted, u64, nc);
+    SCRATCH_ALLOC(keep, uint8_t, nc);
     ASR_HIP_CHECK(ctx, hipMemsetAsync(sizes, 0, (size_t)nc * sizeof(int), s));
     k_comp_sizes<<<grid_for(nv, BLK), BLK, 0, s>>>(parent, nv, label, comp, sizes);
     ASR_CHECK_LAUNCH(ctx);
@@ -1315,10 +1313,10 @@ int asr_mesh_components_count(asr_hip_context* ctx, const float* vertices, i64 n
     }
     k_comp_keep<<<grid_for(nc, BLK), BLK, 0, s>>>(keys_sorted, nc, keep_n, min_size, keep);
     ASR_CHECK_LAUNCH(ctx);
-    MESH_ALLOC(vflag, i64, nv + 1);
-    MESH_ALLOC(voff, i64, nv + 1);
-    MESH_ALLOC(tflag, i64, nt + 1);
-    MESH_ALLOC(toff, i64, nt + 1);
+    SCRATCH_ALLOC(vflag, i64, nv + 1);
+    SCRATCH_ALLOC(voff, i64, nv + 1);
+    SCRATCH_ALLOC(tflag, i64, nt + 1);
+    SCRATCH_ALLOC(toff, i64, nt + 1);
     k_vertex_keep<<<grid_for(nv + 1, BLK), BLK, 0, s>>>(comp, keep, nv, vflag);
     ASR_CHECK_LAUNCH(ctx);
     ASR_TRY(scan_counts(ctx, ctx->scratch, vflag, voff, nv + 1));
@@ -1335,14 +1333,13 @@ int asr_mesh_components_count(asr_hip_context* ctx, const float* vertices, i64 n
     st.t_off = toff;
     *nv_out = st.nv_out;
     *nt_out = st.nt_out;
-    return ASR_HIP_OK;
+    return count_done(ctx, PendingOp::Components);
 }
 
 int asr_mesh_components_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out) {
-    MeshState& st = mstate(ctx);
-    if (st.kind != 2)
+    if (!fill_begin(ctx, PendingOp::Components))
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "components_fill must follow the matching components_count call");
-    st.kind = 0;
+    const ComponentsState& st = mstate(ctx).components;
     hipStream_t s = ctx->stream;
     if (st.nv > 0 && st.nv_out > 0) {
         k_compact_vertices<<<grid_for(st.nv, BLK), BLK, 0, s>>>(st.in_vtx, st.nv, st.v_off, vertices_out);
@@ -1359,32 +1356,27 @@ int asr_mesh_components_fill(asr_hip_context* ctx, float* vertices_out, int32_t*
 
 int asr_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* frame, const float* vertices, i64 nv,
                             const int32_t* triangles, i64 nt, const int8_t* levels, int level, i64* nv_out, i64* nt_out) {
-    MeshState& st = mstate(ctx);
-    st = MeshState();
+    ASR_TRY(count_begin(ctx));
+    SimplifyState& st = mstate(ctx).simplify;
+    st = SimplifyState();
     *nv_out = 0;
     *nt_out = 0;
     if (!levels && (level < 0 || level > ASR_MAX_LEVEL))
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: level %d is not in 0..%d", level, ASR_MAX_LEVEL);
-    if (nv == 0 && nt == 0) {
-        st.kind = 3;
-        return ASR_HIP_OK;
-    }
-    ASR_TRY(ensure_flags(ctx));
-    ctx->scratch.reset();
+    if (nv == 0 && nt == 0) return count_done(ctx, PendingOp::MeshSimplify);
     hipStream_t s = ctx->stream;
-    ASR_TRY(fresh_flags(ctx));
     const i64 nq = 3 * nt;
     if (nv == 0)  // every corner is out of range
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: triangle index out of range");
-    MESH_ALLOC(keys, u64, nv);
-    MESH_ALLOC(ids, int32_t, nv);
-    MESH_ALLOC(keys_s, u64, nv);
-    MESH_ALLOC(ids_s, int32_t, nv);
-    MESH_ALLOC(head, i64, nv + 1);
-    MESH_ALLOC(hoff, i64, nv + 1);
-    MESH_ALLOC(cluster, int32_t, nv);
-    MESH_ALLOC(ckey, u64, nv);
-    MESH_ALLOC(cstart, i64, nv + 1);
+    SCRATCH_ALLOC(keys, u64, nv);
+    SCRATCH_ALLOC(ids, int32_t, nv);
+    SCRATCH_ALLOC(keys_s, u64, nv);
+    SCRATCH_ALLOC(ids_s, int32_t, nv);
+    SCRATCH_ALLOC(head, i64, nv + 1);
+    SCRATCH_ALLOC(hoff, i64, nv + 1);
+    SCRATCH_ALLOC(cluster, int32_t, nv);
+    SCRATCH_ALLOC(ckey, u64, nv);
+    SCRATCH_ALLOC(cstart, i64, nv + 1);
     k_simp_keys<<<grid_for(nv, BLK), BLK, 0, s>>>(*frame, vertices, nv, levels, level, keys, ids, ctx->d_flags);
     ASR_CHECK_LAUNCH(ctx);
     ASR_TRY(sort_pairs(ctx, ctx->scratch, keys, keys_s, ids, ids_s, nv, 64));
@@ -1412,14 +1404,11 @@ int asr_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* frame,
     if (host[F_OUTSIDE]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: vertex outside the frame (or not finite)");
     if (host[F_BAD_INDEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify: triangle index out of range");
     st.nv = nv;
-    if (nt == 0) {  // no triangle: no output vertex, vertex_map is all -1
-        st.kind = 3;
-        return ASR_HIP_OK;
-    }
+    if (nt == 0) return count_done(ctx, PendingOp::MeshSimplify);  // no triangle: no output vertex, vertex_map is all -1
     const int bits = bits_for(nc);
     ASR_TRY(sort_pairs(ctx, ctx->scratch, ck, ck_s, cv, cv_s, nq, bits));
-    MESH_ALLOC(kstart, i64, nc + 1);
-    MESH_ALLOC(cpos, float, nc * 3);
+    SCRATCH_ALLOC(kstart, i64, nc + 1);
+    SCRATCH_ALLOC(cpos, float, nc * 3);
     k_simp_corner_starts<<<grid_for(nc + 1, BLK), BLK, 0, s>>>(ck_s, nq, nc, kstart);
     ASR_CHECK_LAUNCH(ctx);
     k_simp_solve<<<grid_for(nc * 64, BLK), BLK, 0, s>>>(*frame, vertices, triangles, ids_s, ckey, cstart, cv_s, kstart,
@@ -1427,14 +1416,14 @@ int asr_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* frame,
     ASR_CHECK_LAUNCH(ctx);
     // duplicates: the corner buffers are free again (same sizes: 3 nt u32 each)
     u32 *hi = ck, *tid = cv, *tid1 = cv_s, *hi_s = ck_s;
-    MESH_ALLOC(lomid, u64, nt);
-    MESH_ALLOC(lomid1, u64, nt);
-    MESH_ALLOC(lomid2, u64, nt);
-    MESH_ALLOC(tid2, u32, nt);
-    MESH_ALLOC(tflag, i64, nt + 1);
-    MESH_ALLOC(toff, i64, nt + 1);
-    MESH_ALLOC(cref, i64, nc + 1);
-    MESH_ALLOC(coff, i64, nc + 1);
+    SCRATCH_ALLOC(lomid, u64, nt);
+    SCRATCH_ALLOC(lomid1, u64, nt);
+    SCRATCH_ALLOC(lomid2, u64, nt);
+    SCRATCH_ALLOC(tid2, u32, nt);
+    SCRATCH_ALLOC(tflag, i64, nt + 1);
+    SCRATCH_ALLOC(toff, i64, nt + 1);
+    SCRATCH_ALLOC(cref, i64, nc + 1);
+    SCRATCH_ALLOC(coff, i64, nc + 1);
     k_simp_triples<<<grid_for(nt, BLK), BLK, 0, s>>>(triangles, nt, cluster, bits, hi, lomid, tid);
     ASR_CHECK_LAUNCH(ctx);
     ASR_TRY(sort_pairs(ctx, ctx->scratch, hi, hi_s, tid, tid1, nt, bits));
@@ -1452,7 +1441,6 @@ int asr_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* frame,
     ASR_HIP_CHECK(ctx, hipMemcpyAsync(&sizes[0], coff + nc, sizeof(i64), hipMemcpyDeviceToHost, s));
     ASR_HIP_CHECK(ctx, hipMemcpyAsync(&sizes[1], toff + nt, sizeof(i64), hipMemcpyDeviceToHost, s));
     ASR_HIP_CHECK(ctx, hipStreamSynchronize(s));
-    st.kind = 3;
     st.in_tri = triangles;
     st.nt = nt;
     st.nc = nc;
@@ -1462,14 +1450,13 @@ int asr_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* frame,
     st.t_off = toff;
     st.nv_out = *nv_out = sizes[0];
     st.nt_out = *nt_out = sizes[1];
-    return ASR_HIP_OK;
+    return count_done(ctx, PendingOp::MeshSimplify);
 }
 
 int asr_mesh_simplify_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out, int32_t* vertex_map) {
-    MeshState& st = mstate(ctx);
-    if (st.kind != 3)
+    if (!fill_begin(ctx, PendingOp::MeshSimplify))
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_simplify_fill must follow the matching mesh_simplify_count call");
-    st.kind = 0;
+    const SimplifyState& st = mstate(ctx).simplify;
     hipStream_t s = ctx->stream;
     if (st.nv_out > 0) {
         k_simp_out_vertices<<<grid_for(st.nc, BLK), BLK, 0, s>>>(st.cpos, st.nc, st.c_off, vertices_out);
@@ -1496,7 +1483,7 @@ int asr_mesh_sample(asr_hip_context* ctx, const float* vertices, i64 nv, const i
     double* prefix = nullptr;
     if (nt > 0) {  // the corner indices are checked whether or not samples are wanted
         ASR_TRY(fresh_flags(ctx));
-        MESH_ALLOC(area, double, nt);
+        SCRATCH_ALLOC(area, double, nt);
         prefix = arena_alloc<double>(ctx->scratch, (size_t)nt);
         if (!prefix) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
         k_tri_areas<<<grid_for(nt, BLK), BLK, 0, s>>>(vertices, nv, triangles, nt, area, ctx->d_flags);
@@ -1528,12 +1515,12 @@ struct EdgeTable {
 int edge_table(asr_hip_context* ctx, const int32_t* triangles, i64 nt, i64 nv, ull* degenerate, EdgeTable& et) {
     hipStream_t s = ctx->stream;
     const i64 nq = 3 * nt;
-    MESH_ALLOC(keys, u64, nq + 1);
-    MESH_ALLOC(keys_s, u64, nq);
+    SCRATCH_ALLOC(keys, u64, nq + 1);
+    SCRATCH_ALLOC(keys_s, u64, nq);
     i64* head = (i64*)keys;  // the unsorted keys are dead once they are sorted
-    MESH_ALLOC(eoff, i64, nq + 1);
-    MESH_ALLOC(estart, i64, nq + 1);
-    MESH_ALLOC(nvalid, i64, 1);
+    SCRATCH_ALLOC(eoff, i64, nq + 1);
+    SCRATCH_ALLOC(estart, i64, nq + 1);
+    SCRATCH_ALLOC(nvalid, i64, 1);
     if (nq > 0) {
         k_adj_edge_keys<<<grid_for(nq, BLK), BLK, 0, s>>>(triangles, nq, nv, keys, ctx->d_flags, degenerate);
         ASR_CHECK_LAUNCH(ctx);
@@ -1558,36 +1545,30 @@ int read_count_and_flags(asr_hip_context* ctx, const i64* count, i64* host_count
 }  // namespace
 
 int asr_mesh_edges_count(asr_hip_context* ctx, const int32_t* triangles, i64 nt, i64 nv, i64* num_edges) {
-    MeshState& st = mstate(ctx);
-    st = MeshState();
+    ASR_TRY(count_begin(ctx));
+    EdgesState& st = mstate(ctx).edges;
+    st = EdgesState();
     *num_edges = 0;
-    if (nt == 0) {
-        st.kind = 4;
-        return ASR_HIP_OK;
-    }
-    ASR_TRY(ensure_flags(ctx));
-    ctx->scratch.reset();
-    ASR_TRY(fresh_flags(ctx));
+    if (nt == 0) return count_done(ctx, PendingOp::MeshEdges);
     EdgeTable et;
     ASR_TRY(edge_table(ctx, triangles, nt, nv, nullptr, et));
     i64 ne = 0;
     HostFlags host;
     ASR_TRY(read_count_and_flags(ctx, et.count, &ne, host));
     if (host[F_BAD_INDEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_edges: triangle index out of range");
-    st.kind = 4;
     st.num_edges = *num_edges = ne;
-    st.e_keys = et.keys;
-    st.e_start = et.start;
-    st.e_count = et.count;
-    return ASR_HIP_OK;
+    st.keys = et.keys;
+    st.start = et.start;
+    st.count = et.count;
+    return count_done(ctx, PendingOp::MeshEdges);
 }
 
 int asr_mesh_edges_fill(asr_hip_context* ctx, int32_t* edges, int32_t* uses, int32_t* forward) {
-    MeshState& st = mstate(ctx);
-    if (st.kind != 4) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_edges_fill must follow the matching mesh_edges_count call");
-    st.kind = 0;
+    if (!fill_begin(ctx, PendingOp::MeshEdges))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_edges_fill must follow the matching mesh_edges_count call");
+    const EdgesState& st = mstate(ctx).edges;
     if (st.num_edges > 0 && (edges || uses || forward)) {
-        k_adj_edge_out<<<grid_for(st.num_edges, BLK), BLK, 0, ctx->stream>>>(st.e_keys, st.e_start, st.e_count, st.num_edges,
+        k_adj_edge_out<<<grid_for(st.num_edges, BLK), BLK, 0, ctx->stream>>>(st.keys, st.start, st.count, st.num_edges,
                                                                              edges, uses, forward);
         ASR_CHECK_LAUNCH(ctx);
     }
@@ -1596,31 +1577,29 @@ int asr_mesh_edges_fill(asr_hip_context* ctx, int32_t* edges, int32_t* uses, int
 }
 
 int asr_mesh_topology_report(asr_hip_context* ctx, const int32_t* triangles, i64 nt, i64 nv, asr_mesh_topology* out) {
-    mstate(ctx) = MeshState();
     memset(out, 0, sizeof(*out));
     out->num_vertices = nv;
     if (nt == 0) return ASR_HIP_OK;
-    ASR_TRY(ensure_flags(ctx));
     ctx->scratch.reset();
     hipStream_t s = ctx->stream;
     ASR_TRY(fresh_flags(ctx));
-    MESH_ALLOC(cnt, ull, TOPO_COUNTERS);
+    SCRATCH_ALLOC(cnt, ull, TOPO_COUNTERS);
     ASR_HIP_CHECK(ctx, hipMemsetAsync(cnt, 0, TOPO_COUNTERS * sizeof(ull), s));
     EdgeTable et;
     ASR_TRY(edge_table(ctx, triangles, nt, nv, &cnt[TOPO_DEGENERATE], et));
     // the number of edges stays on the device: the kernels below are launched for its upper bound, the sides
     const i64 cap = et.nq;
-    MESH_ALLOC(edges, int32_t, 2 * cap);
-    MESH_ALLOC(uses, int32_t, cap);
-    MESH_ALLOC(forward, int32_t, cap);
+    SCRATCH_ALLOC(edges, int32_t, 2 * cap);
+    SCRATCH_ALLOC(uses, int32_t, cap);
+    SCRATCH_ALLOC(forward, int32_t, cap);
     k_adj_edge_out<<<grid_for(cap, BLK), BLK, 0, s>>>(et.keys, et.start, et.count, cap, edges, uses, forward);
     ASR_CHECK_LAUNCH(ctx);
     k_adj_topo_edges<<<grid_for(cap, BLK), BLK, 0, s>>>(uses, forward, et.count, cap, cnt);
     ASR_CHECK_LAUNCH(ctx);
     if (nv > 0) {  // (nv == 0: every corner is out of range, refused below)
-        MESH_ALLOC(parent_all, int, nv);
-        MESH_ALLOC(parent_bnd, int, nv);
-        MESH_ALLOC(marks, uint8_t, 2 * nv);
+        SCRATCH_ALLOC(parent_all, int, nv);
+        SCRATCH_ALLOC(parent_bnd, int, nv);
+        SCRATCH_ALLOC(marks, uint8_t, 2 * nv);
         ASR_HIP_CHECK(ctx, hipMemsetAsync(marks, 0, (size_t)(2 * nv), s));
         k_uf_init<<<grid_for(nv, BLK), BLK, 0, s>>>(parent_all, nv);
         ASR_CHECK_LAUNCH(ctx);
@@ -1653,8 +1632,6 @@ int asr_mesh_topology_report(asr_hip_context* ctx, const int32_t* triangles, i64
 
 int asr_mesh_smooth(asr_hip_context* ctx, const float* vertices, i64 nv, const int32_t* triangles, i64 nt, int iterations,
                     double lambda, double mu, int boundary, float* vertices_out) {
-    mstate(ctx) = MeshState();
-    ASR_TRY(ensure_flags(ctx));
     ctx->scratch.reset();
     ASR_TRY(fresh_flags(ctx));
     if (nv == 0) {
@@ -1670,15 +1647,15 @@ int asr_mesh_smooth(asr_hip_context* ctx, const float* vertices, i64 nv, const i
     if (host[F_BAD_INDEX]) ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_smooth: triangle index out of range");
     // vertex -> neighbour rows: both directions of every edge, sorted; an entry is (neighbour << 1) | feature
     const i64 np = 2 * ne;
-    MESH_ALLOC(rs, i64, nv + 1);
-    MESH_ALLOC(adj, int32_t, np);
-    MESH_ALLOC(vfeat, uint8_t, nv);
+    SCRATCH_ALLOC(rs, i64, nv + 1);
+    SCRATCH_ALLOC(adj, int32_t, np);
+    SCRATCH_ALLOC(vfeat, uint8_t, nv);
     ASR_HIP_CHECK(ctx, hipMemsetAsync(vfeat, 0, (size_t)nv, s));
     if (ne > 0) {
-        MESH_ALLOC(edges, int32_t, 2 * ne);
-        MESH_ALLOC(uses, int32_t, ne);
-        MESH_ALLOC(pairs, u64, np);
-        MESH_ALLOC(pairs_s, u64, np);
+        SCRATCH_ALLOC(edges, int32_t, 2 * ne);
+        SCRATCH_ALLOC(uses, int32_t, ne);
+        SCRATCH_ALLOC(pairs, u64, np);
+        SCRATCH_ALLOC(pairs_s, u64, np);
         k_adj_edge_out<<<grid_for(ne, BLK), BLK, 0, s>>>(et.keys, et.start, et.count, ne, edges, uses, nullptr);
         ASR_CHECK_LAUNCH(ctx);
         k_adj_csr_pairs<<<grid_for(ne, BLK), BLK, 0, s>>>(edges, uses, ne, pairs, vfeat);
@@ -1692,9 +1669,9 @@ int asr_mesh_smooth(asr_hip_context* ctx, const float* vertices, i64 nv, const i
         ASR_HIP_CHECK(ctx, hipMemsetAsync(rs, 0, (size_t)(nv + 1) * sizeof(i64), s));
     }
     // the rows a whole wave sums: at most np / (SMOOTH_CUT + 1) of them
-    MESH_ALLOC(lflag, i64, nv + 1);
-    MESH_ALLOC(loff, i64, nv + 1);
-    MESH_ALLOC(long_rows, int32_t, np / (SMOOTH_CUT + 1) + 1);
+    SCRATCH_ALLOC(lflag, i64, nv + 1);
+    SCRATCH_ALLOC(loff, i64, nv + 1);
+    SCRATCH_ALLOC(long_rows, int32_t, np / (SMOOTH_CUT + 1) + 1);
     k_smooth_long_flags<<<grid_for(nv + 1, BLK), BLK, 0, s>>>(rs, nv, lflag);
     ASR_CHECK_LAUNCH(ctx);
     ASR_TRY(scan_counts(ctx, ctx->scratch, lflag, loff, nv + 1));
@@ -1731,8 +1708,9 @@ int asr_mesh_smooth(asr_hip_context* ctx, const float* vertices, i64 nv, const i
 
 int asr_mesh_fill_holes_count(asr_hip_context* ctx, const float* vertices, i64 nv, const int32_t* triangles, i64 nt,
                               int max_edges, i64* nv_out, i64* nt_out, asr_mesh_fill_report* report) {
-    MeshState& st = mstate(ctx);
-    st = MeshState();
+    ASR_TRY(count_begin(ctx));
+    FillHolesState& st = mstate(ctx).fill_holes;
+    st = FillHolesState();
     memset(report, 0, sizeof(*report));
     *nv_out = nv;
     *nt_out = nt;
@@ -1740,43 +1718,37 @@ int asr_mesh_fill_holes_count(asr_hip_context* ctx, const float* vertices, i64 n
     st.in_tri = triangles;
     st.nv = st.nv_out = nv;
     st.nt = st.nt_out = nt;
-    if (nt == 0) {
-        st.kind = 5;
-        return ASR_HIP_OK;
-    }
+    if (nt == 0) return count_done(ctx, PendingOp::MeshFillHoles);
     if (nv == 0)  // every corner is out of range
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes: triangle index out of range");
-    ASR_TRY(ensure_flags(ctx));
-    ctx->scratch.reset();
     hipStream_t s = ctx->stream;
-    ASR_TRY(fresh_flags(ctx));
-    MESH_ALLOC(cnt, ull, FILL_COUNTERS);
+    SCRATCH_ALLOC(cnt, ull, FILL_COUNTERS);
     ASR_HIP_CHECK(ctx, hipMemsetAsync(cnt, 0, FILL_COUNTERS * sizeof(ull), s));
     EdgeTable et;
     ASR_TRY(edge_table(ctx, triangles, nt, nv, nullptr, et));
     // as in the topology report the number of edges stays on the device: launches for its upper bound, the sides
     const i64 cap = et.nq;
-    MESH_ALLOC(edges, int32_t, 2 * cap);
-    MESH_ALLOC(uses, int32_t, cap);
-    MESH_ALLOC(forward, int32_t, cap);
-    MESH_ALLOC(parent, int, nv);
-    MESH_ALLOC(ints, int, 6 * nv);  // out_deg, in_deg, len, bad, succ, start: zeroed together
+    SCRATCH_ALLOC(edges, int32_t, 2 * cap);
+    SCRATCH_ALLOC(uses, int32_t, cap);
+    SCRATCH_ALLOC(forward, int32_t, cap);
+    SCRATCH_ALLOC(parent, int, nv);
+    SCRATCH_ALLOC(ints, int, 6 * nv);  // out_deg, in_deg, len, bad, succ, start: zeroed together
     int *out_deg = ints, *in_deg = ints + nv, *len = ints + 2 * nv, *bad = ints + 3 * nv, *succ = ints + 4 * nv,
         *start = ints + 5 * nv;
-    MESH_ALLOC(root_of, int, nv);
-    MESH_ALLOC(marks, uint8_t, 2 * nv);  // on the boundary; rim id of a filled rim
+    SCRATCH_ALLOC(root_of, int, nv);
+    SCRATCH_ALLOC(marks, uint8_t, 2 * nv);  // on the boundary; rim id of a filled rim
     uint8_t *on_bnd = marks, *filled_rim = marks + nv;
-    MESH_ALLOC(hub_flag, i64, nv + 1);
-    MESH_ALLOC(tri_count, i64, nv + 1);
-    MESH_ALLOC(long_flag, i64, nv + 1);
-    MESH_ALLOC(hub_off, i64, nv + 1);
-    MESH_ALLOC(tri_off, i64, nv + 1);
-    MESH_ALLOC(long_off, i64, nv + 1);
-    MESH_ALLOC(keys, u64, nv);
-    MESH_ALLOC(keys_s, u64, nv);
+    SCRATCH_ALLOC(hub_flag, i64, nv + 1);
+    SCRATCH_ALLOC(tri_count, i64, nv + 1);
+    SCRATCH_ALLOC(long_flag, i64, nv + 1);
+    SCRATCH_ALLOC(hub_off, i64, nv + 1);
+    SCRATCH_ALLOC(tri_off, i64, nv + 1);
+    SCRATCH_ALLOC(long_off, i64, nv + 1);
+    SCRATCH_ALLOC(keys, u64, nv);
+    SCRATCH_ALLOC(keys_s, u64, nv);
     // a rim with a hub has at least 4 vertices, a long one more than FILL_CUT, and rims share no vertex
-    MESH_ALLOC(hub_rims, int32_t, nv / 4 + 1);
-    MESH_ALLOC(long_rims, int32_t, nv / (FILL_CUT + 1) + 1);
+    SCRATCH_ALLOC(hub_rims, int32_t, nv / 4 + 1);
+    SCRATCH_ALLOC(long_rims, int32_t, nv / (FILL_CUT + 1) + 1);
     ASR_HIP_CHECK(ctx, hipMemsetAsync(ints, 0, (size_t)(6 * nv) * sizeof(int), s));
     ASR_HIP_CHECK(ctx, hipMemsetAsync(marks, 0, (size_t)(2 * nv), s));
     k_adj_edge_out<<<grid_for(cap, BLK), BLK, 0, s>>>(et.keys, et.start, et.count, cap, edges, uses, forward);
@@ -1821,27 +1793,25 @@ int asr_mesh_fill_holes_count(asr_hip_context* ctx, const float* vertices, i64 n
     report->not_simple = (i64)h[FILL_NOT_SIMPLE];
     report->new_vertices = sizes[0];
     report->new_triangles = sizes[1];
-    st.kind = 5;
     st.nv_out = *nv_out = nv + sizes[0];
     st.nt_out = *nt_out = nt + sizes[1];
-    st.f_rim_vertices = (i64)h[FILL_RIM_VERTICES];
-    st.f_long = sizes[2];
-    st.f_keys = keys_s;
-    st.f_len = len;
-    st.f_succ = succ;
-    st.f_start = start;
-    st.f_hub_off = hub_off;
-    st.f_tri_off = tri_off;
-    st.f_hub_rims = hub_rims;
-    st.f_long_rims = long_rims;
-    return ASR_HIP_OK;
+    st.rim_vertices = (i64)h[FILL_RIM_VERTICES];
+    st.num_long = sizes[2];
+    st.keys = keys_s;
+    st.len = len;
+    st.succ = succ;
+    st.start = start;
+    st.hub_off = hub_off;
+    st.tri_off = tri_off;
+    st.hub_rims = hub_rims;
+    st.long_rims = long_rims;
+    return count_done(ctx, PendingOp::MeshFillHoles);
 }
 
 int asr_mesh_fill_holes_fill(asr_hip_context* ctx, float* vertices_out, int32_t* triangles_out) {
-    MeshState& st = mstate(ctx);
-    if (st.kind != 5)
+    if (!fill_begin(ctx, PendingOp::MeshFillHoles))
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "mesh_fill_holes_fill must follow the matching mesh_fill_holes_count call");
-    st.kind = 0;
+    const FillHolesState& st = mstate(ctx).fill_holes;
     hipStream_t s = ctx->stream;
     if (st.nv > 0)
         ASR_HIP_CHECK(ctx, hipMemcpyAsync(vertices_out, st.in_vtx, (size_t)st.nv * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1851,18 +1821,17 @@ int asr_mesh_fill_holes_fill(asr_hip_context* ctx, float* vertices_out, int32_t*
     const i64 nhubs = st.nv_out - st.nv;
     if (nhubs > 0) {
         float* hubs = vertices_out + 3 * st.nv;
-        k_fill_hub<<<grid_for(nhubs, BLK), BLK, 0, s>>>(st.in_vtx, st.f_keys, st.f_len, st.f_start, st.f_hub_rims, nhubs, hubs);
+        k_fill_hub<<<grid_for(nhubs, BLK), BLK, 0, s>>>(st.in_vtx, st.keys, st.len, st.start, st.hub_rims, nhubs, hubs);
         ASR_CHECK_LAUNCH(ctx);
-        if (st.f_long > 0) {
-            k_fill_hub_long<<<grid_for(st.f_long * 64, BLK), BLK, 0, s>>>(st.in_vtx, st.f_keys, st.f_len, st.f_start,
-                                                                          st.f_hub_off, st.f_long_rims, st.f_long, hubs);
+        if (st.num_long > 0) {
+            k_fill_hub_long<<<grid_for(st.num_long * 64, BLK), BLK, 0, s>>>(st.in_vtx, st.keys, st.len, st.start,
+                                                                            st.hub_off, st.long_rims, st.num_long, hubs);
             ASR_CHECK_LAUNCH(ctx);
         }
     }
     if (st.nt_out > st.nt) {
-        k_fill_emit<<<grid_for(st.f_rim_vertices, BLK), BLK, 0, s>>>(st.f_keys, st.f_rim_vertices, st.f_len, st.f_start,
-                                                                     st.f_succ, st.f_hub_off, st.f_tri_off, st.nv,
-                                                                     triangles_out + 3 * st.nt);
+        k_fill_emit<<<grid_for(st.rim_vertices, BLK), BLK, 0, s>>>(st.keys, st.rim_vertices, st.len, st.start, st.succ,
+                                                                   st.hub_off, st.tri_off, st.nv, triangles_out + 3 * st.nt);
         ASR_CHECK_LAUNCH(ctx);
     }
     ASR_HIP_CHECK(ctx, hipStreamSynchronize(s));

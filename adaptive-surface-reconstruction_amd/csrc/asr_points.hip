@@ -252,10 +252,6 @@ __global__ void k_merge_map(const u64* keys, const int32_t* ids, const i64* off,
     map[ids[r]] = keys[r] == 0 ? -1 : (int32_t)(off[r + 1] - 1);
 }
 
-#define MERGE_ALLOC(var, T, count)                          \
-    T* var = arena_alloc<T>(ctx->scratch, (size_t)(count)); \
-    if (!var) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed")
-
 // ------------------------------------------------------------------------------------------
 // Point normals (asr_hip_point_normals): one thread per point, everything in f64 from the f32
 // coordinates.  Two passes over the row: the mean of the m valid neighbours, then the six centred sums, both in slot order
@@ -536,28 +532,24 @@ __global__ void k_orient_flip(const float* nrm, i64 n, const uint8_t* __restrict
 int asr_points_merge_count(asr_hip_context* ctx, const asr_octree_frame* frame, const float* points, i64 n,
                            const float* normals, const float* radii, const float* attributes, int c, const int8_t* levels,
                            int level, int split_sides, i64* num_clusters, asr_points_merge_report* report) {
+    ASR_TRY(count_begin(ctx));
     AsrMergeState& st = ctx->merge;
     st = AsrMergeState();
     *num_clusters = 0;
     if (report) *report = asr_points_merge_report{0, 0, 0, 0};
     st.points = points, st.normals = normals, st.radii = radii, st.attributes = attributes, st.channels = c;
     st.n = n;
-    if (n == 0) {
-        st.valid = true;
-        return ASR_HIP_OK;
-    }
-    ctx->scratch.reset();
+    if (n == 0) return count_done(ctx, PendingOp::PointsMerge);
     hipStream_t s = ctx->stream;
-    ASR_TRY(fresh_flags(ctx));
     int* flags = ctx->d_flags;
-    MERGE_ALLOC(keys, u64, n);
-    MERGE_ALLOC(ids, int32_t, n);
-    MERGE_ALLOC(keys_s, u64, n);
-    MERGE_ALLOC(ids_s, int32_t, n);
-    MERGE_ALLOC(head, i64, n + 1);
-    MERGE_ALLOC(off, i64, n + 1);
-    MERGE_ALLOC(starts, i64, n + 1);
-    MERGE_ALLOC(long_list, int32_t, n / (CUT + 1) + 1);
+    SCRATCH_ALLOC(keys, u64, n);
+    SCRATCH_ALLOC(ids, int32_t, n);
+    SCRATCH_ALLOC(keys_s, u64, n);
+    SCRATCH_ALLOC(ids_s, int32_t, n);
+    SCRATCH_ALLOC(head, i64, n + 1);
+    SCRATCH_ALLOC(off, i64, n + 1);
+    SCRATCH_ALLOC(starts, i64, n + 1);
+    SCRATCH_ALLOC(long_list, int32_t, n / (CUT + 1) + 1);
     k_merge_keys<<<grid_for(n, BLK), BLK, 0, s>>>(*frame, points, n, levels, level, keys, ids, flags);
     ASR_CHECK_LAUNCH(ctx);
     // the marker bit of a level-l key is bit 3 l
@@ -567,11 +559,11 @@ int asr_points_merge_count(asr_hip_context* ctx, const asr_octree_frame* frame, 
     ASR_TRY(scan_counts(ctx, ctx->scratch, head, off, n + 1));
     const int32_t* members = ids_s;
     if (split_sides) {
-        MERGE_ALLOC(side, uint8_t, n);
-        MERGE_ALLOC(side_p, uint8_t, n);
-        MERGE_ALLOC(ids_p, int32_t, n);
-        MERGE_ALLOC(zero, i64, n + 1);
-        MERGE_ALLOC(zoff, i64, n + 1);
+        SCRATCH_ALLOC(side, uint8_t, n);
+        SCRATCH_ALLOC(side_p, uint8_t, n);
+        SCRATCH_ALLOC(ids_p, int32_t, n);
+        SCRATCH_ALLOC(zero, i64, n + 1);
+        SCRATCH_ALLOC(zoff, i64, n + 1);
         k_merge_starts<<<grid_for(n + 1, BLK), BLK, 0, s>>>(off, n, starts, nullptr);  // of the cells
         ASR_CHECK_LAUNCH(ctx);
         k_merge_sides<<<grid_for(n + 1, BLK), BLK, 0, s>>>(keys_s, ids_s, n, off, starts, normals, side, zero);
@@ -595,19 +587,18 @@ int asr_points_merge_count(asr_hip_context* ctx, const asr_octree_frame* frame, 
     st.clusters = host[F_MERGE_CLUSTERS];
     st.num_long = host[F_MERGE_LONG];
     st.keys = keys_s, st.ids = members, st.offsets = off, st.starts = starts, st.long_list = long_list;
-    st.valid = true;
     *num_clusters = st.clusters;
     if (report)
         *report = asr_points_merge_report{st.clusters, (i64)host[F_MERGE_DROPPED], (i64)host[F_MERGE_LARGEST],
                                           (i64)host[F_MERGE_SPLIT]};
-    return ASR_HIP_OK;
+    return count_done(ctx, PendingOp::PointsMerge);
 }
 
 int asr_points_merge_fill(asr_hip_context* ctx, float* points_out, float* normals_out, float* radii_out,
                           float* attributes_out, int32_t* counts_out, int32_t* cluster_out) {
     AsrMergeState& st = ctx->merge;
-    if (!st.valid) ASR_FAIL(ctx, ASR_HIP_EINVAL, "points_merge_fill must follow the matching points_merge_count call");
-    st.valid = false;
+    if (!fill_begin(ctx, PendingOp::PointsMerge))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "points_merge_fill must follow the matching points_merge_count call");
     if (st.n == 0) return ASR_HIP_OK;
     hipStream_t s = ctx->stream;
     // an output whose input was not given stays unwritten
@@ -664,14 +655,14 @@ int asr_points_orient(asr_hip_context* ctx, const float* points, const float* no
         report[2] = host[F_ORIENT_SKIPPED];
         return ASR_HIP_OK;
     }
-    MERGE_ALLOC(parent, int32_t, n);
-    MERGE_ALLOC(par, uint8_t, n);
-    MERGE_ALLOC(hook, int32_t, n);
-    MERGE_ALLOC(hook_par, uint8_t, n);
-    MERGE_ALLOC(root, int32_t, n);
-    MERGE_ALLOC(root_par, uint8_t, n);
-    MERGE_ALLOC(best, u64, n);
-    MERGE_ALLOC(flips_tmp, uint8_t, n);
+    SCRATCH_ALLOC(parent, int32_t, n);
+    SCRATCH_ALLOC(par, uint8_t, n);
+    SCRATCH_ALLOC(hook, int32_t, n);
+    SCRATCH_ALLOC(hook_par, uint8_t, n);
+    SCRATCH_ALLOC(root, int32_t, n);
+    SCRATCH_ALLOC(root_par, uint8_t, n);
+    SCRATCH_ALLOC(best, u64, n);
+    SCRATCH_ALLOC(flips_tmp, uint8_t, n);
     u64* top = best;  // the offers are over when the top points are looked for
     uint8_t* flips = flips_out ? flips_out : flips_tmp;
     k_orient_init<<<grid_for(n, BLK), BLK, 0, s>>>(normals, n, parent, par, flags);

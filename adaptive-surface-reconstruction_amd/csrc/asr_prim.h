@@ -78,6 +78,26 @@ static inline int fresh_flags(asr_hip_context* ctx) {
     ctx->d_flags = ctx->d_flags_base + (size_t)FLAG_BLOCK * ctx->flags_next++;
     return ASR_HIP_OK;
 }
+// How a _count call that keeps its work in the scratch arena starts: nothing is pending any more (asr_pending.h), the
+// arena is recycled, the counters are fresh.  Before any early return, so that every count of an operator starts alike.
+static inline int count_begin(asr_hip_context* ctx) {
+    pending_begin(ctx->pending);
+    ctx->scratch.reset();
+    return fresh_flags(ctx);
+}
+// how a _count call that succeeded returns, the early returns for empty input included
+static inline int count_done(asr_hip_context* ctx, PendingOp op) {
+    pending_commit(ctx->pending, op, ctx->scratch.generation);
+    return ASR_HIP_OK;
+}
+// _fill: false unless it completes the most recent successful count, `op`'s, in a scratch arena nobody has recycled
+static inline bool fill_begin(asr_hip_context* ctx, PendingOp op) {
+    return pending_claim(ctx->pending, op, ctx->scratch.generation);
+}
+// T* var = `count` elements of the context's scratch arena, or the function fails
+#define SCRATCH_ALLOC(var, T, count)                        \
+    T* var = arena_alloc<T>(ctx->scratch, (size_t)(count)); \
+    if (!var) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed")
 static inline int read_flags(asr_hip_context* ctx, HostFlags& host) {
     ASR_HIP_CHECK(ctx, hipMemcpyAsync(host.v, ctx->d_flags, FLAG_READ * sizeof(int), hipMemcpyDeviceToHost,
                                       ctx->stream));

@@ -12,6 +12,22 @@
  *   - dtypes follow the reference tensors (cpp/lib/asr.cpp:179-312): indices int32, kernel
  *     indices uint8, row splits int64, keys uint64, features float32
  *
+ * Count / fill pairs
+ *   Eight operators come as X_count, which does the work, reports the output sizes and parks device arrays in the
+ *   context's scratch arena, and X_fill, which writes the outputs from them: asr_hip_multi_radius_search, _dual_cells
+ *   (both count forms), _contour, _components, _mesh_simplify, _mesh_edges, _mesh_fill_holes and _points_merge.
+ *   A context holds ONE pending count.  X_fill completes the most recent successful _count on that context, which must
+ *   be X's own, and does so once.  It is refused -- ASR_HIP_EINVAL "... must follow the matching ... call", on the host,
+ *   nothing is launched -- when no count is pending, when the last count was another operator's or failed (a count that
+ *   begins voids the pending one, whatever becomes of it), and when any call that RECYCLES THE SCRATCH ARENA ran on the
+ *   context in between: the parked arrays then belong to that call.  Such calls are every _count of these pairs, both
+ *   calls of the grid_neighbors and grid_coarsen pairs, the octree builds and the asr_hip_implicit_* entry points, and
+ *   every single-call operator that needs device temporaries (the searches: knn_*, radius_neighbor_count,
+ *   nearest_point, point_attributes_at; row_groups, invert_neighbors_list, sparse_conv_plan_create,
+ *   continuous_conv_f32; mesh_sample, mesh_topology, mesh_smooth; normals_orient).  Take every call that enqueues work
+ *   on the context for one of them; the calls that only read or set host state (last_error, options, set_stream, ...)
+ *   never are.  The input arrays of X_count must stay alive and unchanged until X_fill returns: fill reads them again.
+ *
  * The reference has no C ABI (the ASR_API_EXTERN_C macros of cpp/lib/asr_config.h:18-28 are
  * unused); each entry point cites the reference interface it stands in for.
  */
@@ -153,26 +169,25 @@ int asr_hip_octree_get(asr_hip_context* ctx, uint64_t* nodes_out_dev, uint64_t* 
 /* ---- dual cells ("next" row D.1): asr::CreateDualVertexIndices (cpp/lib/grid.cpp:316-459) ------ */
 /* For the octree of the last asr_hip_octree_build / asr_hip_implicit_build of this context.
  * count returns the number of dual cells D; fill writes [D,8] leaf indices (leaf order x corner
- * order), the `dual_vertex_indices` consumed by CreateTriangleMesh (cpp/lib/asr.cpp:154,340). */
+ * order), the `dual_vertex_indices` consumed by CreateTriangleMesh (cpp/lib/asr.cpp:154,340).  A count / fill pair
+ * ("Count / fill pairs" at the top of this file). */
 int asr_hip_dual_cells_count(asr_hip_context* ctx, int64_t* num_cells);
 /* the same for ANY octree given by its sorted node / leaf keys (asr_hip_octree_get): the pybind Octree handle
- * (cpp/pybind/module.cpp:230-235) stays usable however many trees were built since.  The arrays must stay valid
- * until the fill call. */
+ * (cpp/pybind/module.cpp:230-235) stays usable however many trees were built since. */
 int asr_hip_dual_cells_count_for(asr_hip_context* ctx, const uint64_t* nodes_dev, int64_t num_nodes,
                                  const uint64_t* leaves_dev, int64_t num_leaves, int64_t* num_cells);
 int asr_hip_dual_cells_fill(asr_hip_context* ctx, int64_t* dual_vertex_indices_out_dev);
 
 /* ---- dual contouring ("next" row D.2): asr::CreateTriangleMesh (cpp/lib/contouring.cpp:29-460) ---- */
 /* values [V,2] (signed, unsigned), dual_vertex_indices [D,8] int64, node_positions [V,3]; all
- * device pointers that must stay valid until the fill call.  count returns the mesh sizes, fill
+ * device pointers.  A count / fill pair ("Count / fill pairs" at the top): count returns the mesh sizes, fill
  * writes vertices f32[M,3] (one per active dual cell in dual order, then the fan centres in
  * emission order) and triangles i32[T,3] in the reference's serial emission order, including the
  * corner order it derives from libstdc++'s unordered_set iteration (see csrc/asr_uset.h).
  * count checks on the device, before any load through them, that every dual vertex index lies in
  * [0, num_values): ASR_HIP_EINVAL "contour: dual vertex index out of range" otherwise.  More than 29 active
  * cells around one crossing edge (no face-balanced octree has more than 8) is ASR_HIP_ELOGIC from count; cells
- * around an edge that cannot be ordered are the reference's "cannot sort duals", ASR_HIP_ELOGIC from fill.
- * fill is refused after a count that failed. */
+ * around an edge that cannot be ordered are the reference's "cannot sort duals", ASR_HIP_ELOGIC from fill. */
 int asr_hip_contour_count(asr_hip_context* ctx, const float* values_dev, int64_t num_values,
                           const int64_t* dual_vertex_indices_dev, int64_t num_duals,
                           const float* node_positions_dev, float value_threshold,
@@ -182,7 +197,8 @@ int asr_hip_contour_fill(asr_hip_context* ctx, float* vertices_out_dev, int32_t*
 /* ---- component filter ("next" row D.3): asr::RemoveConnectedComponents
  * (cpp/lib/postprocess.cpp:141-176).  Keeps the keep_n largest components (size in vertices,
  * ties -> the component found later first, like std::greater on (size, label)) that have at least
- * min_size vertices; compacts vertices and re-indexes triangles, order preserving. */
+ * min_size vertices; compacts vertices and re-indexes triangles, order preserving.  A count / fill pair ("Count /
+ * fill pairs" at the top). */
 int asr_hip_components_count(asr_hip_context* ctx, const float* vertices_dev, int64_t num_vertices,
                              const int32_t* triangles_dev, int64_t num_triangles, int64_t keep_n,
                              int64_t min_size, int64_t* num_vertices_out, int64_t* num_triangles_out);
@@ -238,7 +254,8 @@ int asr_hip_voxel_info(asr_hip_context* ctx, const asr_octree_frame* frame,
 
 /* ---- a8: ComputeAggregationNeighborsAndScaleCompatibility (cpp/lib/nsearch.cpp:107-162) - */
 /* Members of row q: points with ((dx*dx+dy*dy)+dz*dz) < size[q]^2, ordered by (distance,
- * index); dist = squared distance; compat = (min(size, 2 r)/max(size, 2 r))^2. */
+ * index); dist = squared distance; compat = (min(size, 2 r)/max(size, 2 r))^2.  A count / fill pair ("Count / fill
+ * pairs" at the top); fill must name the n and v of its count. */
 int asr_hip_multi_radius_search_count(asr_hip_context* ctx, const asr_octree_frame* frame,
                                       const float* points_dev, int64_t n,
                                       const float* centers_dev, const float* sizes_dev,
@@ -536,8 +553,8 @@ int asr_hip_mesh_sample(asr_hip_context* ctx, const float* vertices_dev, int64_t
  *     same inputs give the same bits on every run.
  * num_vertices == 0 or num_triangles == 0 is valid and gives an empty result (the vertices are still checked).
  * Sizes < 2^31 vertices and < 2^31 / 3 triangles.  _count reads the cluster count and the error flags back once and
- * the two output sizes once; scratch comes from the context arena and stays valid until _fill, which must be the next
- * mesh call on the context.  vertex_map_out_dev [num_vertices] may be NULL.
+ * the two output sizes once; a count / fill pair ("Count / fill pairs" at the top).  vertex_map_out_dev [num_vertices]
+ * may be NULL.
  * Clustering can create non-manifold edges and vertices (two sheets closer than a cell merge); the result is not
  * filtered -- running asr_hip_components_* afterwards is the caller's choice. */
 int asr_hip_mesh_simplify_count(asr_hip_context* ctx, const asr_octree_frame* frame, const float* vertices_dev,
@@ -557,9 +574,8 @@ int asr_hip_mesh_simplify_fill(asr_hip_context* ctx, float* vertices_out_dev, in
  *     INCONSISTENT when uses == 2 and forward != 1 (its two triangles disagree about the orientation), and a FEATURE
  *     edge when uses != 2.  A FEATURE VERTEX is an end of a feature edge.
  *
- * The edge table.  Count / fill pair like asr_hip_mesh_simplify_*: _count reads the number of edges and the error flag
- * back once; scratch comes from the context arena and stays valid until _fill, which must be the next mesh call on the
- * context.  edges_out_dev [E,2] = (lo, hi), uses_out_dev [E], forward_out_dev [E]; any of them may be NULL.
+ * The edge table.  A count / fill pair ("Count / fill pairs" at the top): _count reads the number of edges and the
+ * error flag back once.  edges_out_dev [E,2] = (lo, hi), uses_out_dev [E], forward_out_dev [E]; any of them may be NULL.
  * num_triangles == 0 gives E == 0.  Integers only: the same inputs give the same bits. */
 int asr_hip_mesh_edges_count(asr_hip_context* ctx, const int32_t* triangles_dev, int64_t num_triangles,
                              int64_t num_vertices, int64_t* num_edges_out);
@@ -631,9 +647,8 @@ int asr_hip_mesh_smooth(asr_hip_context* ctx, const float* vertices_dev, int64_t
  *     (whatever its length), new_vertices (hubs), new_triangles.  Every filled rim raises the Euler characteristic by
  *     exactly 1; an edge-manifold, oriented mesh with simple rims only and max_edges >= its longest rim comes out
  *     watertight.
- * Count / fill pair like asr_hip_mesh_simplify_*: _count reads the report, the sizes and the error flags back once;
- * scratch comes from the context arena and stays valid until _fill, which must be the next mesh call on the context
- * and also copies the input arrays (the outputs must not overlap the inputs).
+ * A count / fill pair ("Count / fill pairs" at the top): _count reads the report, the sizes and the error flags back
+ * once; _fill also copies the input arrays (the outputs must not overlap the inputs).
  * ASR_HIP_EINVAL: a corner out of range ("out of range"); a vertex ON A FILLED RIM that is not finite -- no other
  * vertex is read; a result that no longer fits the sizes above.  num_triangles == 0, or no boundary at all, copies the
  * input and gives a zero report.  The same inputs give the same bits on every run. */
@@ -646,7 +661,7 @@ int asr_hip_mesh_fill_holes_count(asr_hip_context* ctx, const float* vertices_de
 int asr_hip_mesh_fill_holes_fill(asr_hip_context* ctx, float* vertices_out_dev, int32_t* triangles_out_dev);
 /* ---- point merge: one point per occupied octree cell (not in the reference).
  * Reduces a cloud before the reconstruction: all points that share a cell of the frame's octree become one point, the
- * mean of its members.  Count / fill pair like asr_hip_mesh_simplify_*; the contract, which tests/points_merge_ref.py
+ * mean of its members.  A count / fill pair ("Count / fill pairs" at the top); the contract, which tests/points_merge_ref.py
  * restates in numpy:
  *   Inputs: points_dev [n,3]; optional (NULL: absent) normals_dev [n,3], radii_dev [n] and attributes_dev [n,c] with
  *     1 <= c <= ASR_MAX_ATTRIBUTE_CHANNELS (c is ignored without attributes).  0 <= n < 2^31; n == 0 is valid and gives
@@ -681,9 +696,8 @@ int asr_hip_mesh_fill_holes_fill(asr_hip_context* ctx, float* vertices_out_dev, 
  *   Report: clusters, dropped points, members of the largest cluster, cells that were split into two sides.
  * _count enqueues the key pass, one stable radix sort of (key, index) -- its last bit taken from `level`, all 64 bits
  * with levels_dev --, the side partition and the cluster scan, and reads the cluster count, the error flags and the
- * report back once; scratch comes from the context arena and stays valid until _fill, which must be the next call of
- * this family on the context and runs the reduction.  The input arrays must still be alive then.  Every output pointer
- * of _fill, and report, may be NULL; an output whose input was not given is not written. */
+ * report back once; _fill runs the reduction.  Every output pointer of _fill, and report, may be NULL; an output whose
+ * input was not given is not written. */
 #define ASR_MERGE_LONG_CLUSTER 128
 typedef struct asr_points_merge_report {
     int64_t clusters, dropped, largest_cluster, split_cells;
