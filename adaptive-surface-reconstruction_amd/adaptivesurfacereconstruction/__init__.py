@@ -473,6 +473,64 @@ def merge_points(points, normals=None, radii=None, attributes=None, cell_size=No
             "cluster": host(cluster), "report": report, "cell_size": used}
 
 
+def register_points(source, target, target_normals=None, init=None, max_distance=None, max_iterations=50,
+                    rotation_tolerance=1e-7, translation_tolerance=None):
+    """Not in the reference's module.  Rigid registration of one scan onto another by ICP on the GPU (DESIGN.md 4.16,
+    asr_hip.ops.register_points): finds the rotation and translation that move `source` [M,3] into the coordinate frame
+    of `target` [N,3], starting from `init` (a 4x4 or 3x4 rigid transform, default: the identity) -- a local method, the
+    scans must overlap and be roughly aligned already.  Each iteration pairs every moved source point with its exact
+    nearest target point within max_distance and solves the linearised alignment: point-to-plane when target_normals
+    [N,3] are given (a few iterations), point-to-point without them (dozens).  Source points without a target point
+    within max_distance take no part, so a partial overlap is fine.
+      max_distance           None: 5 % of the diagonal of the target's bounding box
+      translation_tolerance  None: 1e-7 of that diagonal; the loop stops once an update rotates by at most
+                             rotation_tolerance (radians) and moves by at most translation_tolerance
+    The octree frame is the one around the target's bounding box (with KDTree's margin); non-finite target points are a
+    ValueError, non-finite source points take no part.
+    -> {'transform': f64 [4,4], 'fitness': paired share of the source points, 'rmse': of the pairs' distances, both of
+    the last evaluated step, 'iterations', 'converged', 'degenerate' (the pairs do not determine a rigid motion, e.g. a
+    planar target in point-to-plane mode: the transform is the last determined one), 'pairs'}."""
+    target = _f32(target, "target", "[N,3]", 2, 3)
+    source = _f32(source, "source", "[M,3]", 2, 3)
+    if target_normals is not None:
+        target_normals = _f32(target_normals, "target_normals", "[N,3]", 2, 3)
+    if target.shape[0] == 0:
+        raise ValueError("target is empty")
+    if not np.isfinite(target).all():
+        raise ValueError("target points must be finite")
+    diagonal = float(np.linalg.norm(target.max(0).astype(np.float64) - target.min(0).astype(np.float64)))
+    if max_distance is None:
+        max_distance = 0.05 * diagonal
+    if translation_tolerance is None:
+        translation_tolerance = 1e-7 * diagonal
+    _ops.check_register_arguments(target, target_normals, source, max_distance, init, max_iterations, rotation_tolerance,
+                                  translation_tolerance)
+    frame = _margin_frame(target)
+    dev = torch.device("cuda")
+    t = lambda a: None if a is None else torch.from_numpy(a).to(dev)  # noqa: E731
+    transform, report = _ops.register_points(frame, t(target), t(target_normals), t(source), max_distance, init,
+                                             max_iterations, rotation_tolerance, translation_tolerance)
+    report["transform"] = np.vstack([transform, [0.0, 0.0, 0.0, 1.0]])
+    return report
+
+
+def transform_points(points, transform, normals=None):
+    """Applies a rigid transform (4x4 or 3x4, as register_points returns it) to points [N,3] with the arithmetic of the
+    registration itself: every coordinate is ((R0 x + R1 y) + R2 z) + t in f64, rounded once to f32.  Normals are rotated
+    only.  -> points f32 [N,3], or (points, normals) when normals are given."""
+    t = _ops._transform12(transform)
+    points = _f32(points, "points", "[N,3]", 2, 3)
+    p = points.astype(np.float64)
+    moved = (((t[:, 0] * p[:, 0:1] + t[:, 1] * p[:, 1:2]) + t[:, 2] * p[:, 2:3]) + t[:, 3]).astype(np.float32)
+    if normals is None:
+        return moved
+    normals = _f32(normals, "normals", "[N,3]", 2, 3)
+    if normals.shape[0] != points.shape[0]:
+        raise ValueError("normals must have shape [N,3]")
+    n = normals.astype(np.float64)
+    return moved, ((t[:, 0] * n[:, 0:1] + t[:, 1] * n[:, 1:2]) + t[:, 2] * n[:, 2:3]).astype(np.float32)
+
+
 def smooth_mesh(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, boundary="along"):
     """Not in the reference's module.  Taubin smoothing of any triangle mesh (asr_hip.ops.mesh_smooth): `iterations`
     times a step p += lam (mean of the edge neighbours - p) and the same step with mu < -lam, which undoes the shrinking

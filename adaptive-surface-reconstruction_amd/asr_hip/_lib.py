@@ -151,6 +151,38 @@ class PointsMergeReport(ctypes.Structure):
     _fields_ = [(name, ctypes.c_int64) for name in ("clusters", "dropped", "largest_cluster", "split_cells")]
 
 
+class IcpSums(ctypes.Structure):
+    _fields_ = [
+        ("ata", ctypes.c_double * 21),
+        ("atb", ctypes.c_double * 6),
+        ("sq_residual", ctypes.c_double),
+        ("sq_distance", ctypes.c_double),
+        ("pairs", ctypes.c_int64),
+        ("mode", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class IcpParams(ctypes.Structure):
+    _fields_ = [
+        ("max_distance", ctypes.c_float),
+        ("max_iterations", ctypes.c_int),
+        ("rotation_tolerance", ctypes.c_double),
+        ("translation_tolerance", ctypes.c_double),
+    ]
+
+
+class IcpReport(ctypes.Structure):
+    _fields_ = [
+        ("iterations", ctypes.c_int),
+        ("converged", ctypes.c_int),
+        ("degenerate", ctypes.c_int),
+        ("pairs", ctypes.c_int64),
+        ("rmse", ctypes.c_double),
+        ("fitness", ctypes.c_double),
+    ]
+
+
 # every symbol declared in include/asr_hip.h (tests/test_abi.py checks the list against the header)
 EXPORTS = [
     "asr_hip_context_create", "asr_hip_context_destroy", "asr_hip_context_set_stream",
@@ -174,6 +206,7 @@ EXPORTS = [
     "asr_hip_mesh_fill_holes_count", "asr_hip_mesh_fill_holes_fill",
     "asr_hip_points_merge_count", "asr_hip_points_merge_fill",
     "asr_hip_knn_index", "asr_hip_point_normals", "asr_hip_normals_orient",
+    "asr_hip_icp_step", "asr_hip_icp_update", "asr_hip_register_points",
     "asr_hip_implicit_build",
     "asr_hip_implicit_network", "asr_hip_implicit_aggregate", "asr_hip_implicit_forward", "asr_hip_implicit_get",
     "asr_hip_implicit_stage_ms", "asr_hip_implicit_query",
@@ -207,7 +240,8 @@ def load():
                           ("asr_implicit_sizes", ImplicitSizes), ("asr_shard_comm", ShardComm),
                           ("asr_shard_stats", ShardStats), ("asr_mesh_topology", MeshTopology),
                           ("asr_mesh_fill_report", MeshFillReport),
-                          ("asr_points_merge_report", PointsMergeReport)):
+                          ("asr_points_merge_report", PointsMergeReport), ("asr_icp_sums", IcpSums),
+                          ("asr_icp_params", IcpParams), ("asr_icp_report", IcpReport)):
             if lib.asr_hip_struct_size(name.encode()) != ctypes.sizeof(cls):
                 raise AsrHipError("ABI mismatch: struct %s has a different size in libasr_hip.so"
                                   % name)
@@ -236,6 +270,14 @@ def load():
         lib.asr_hip_knn_index.argtypes = [vp, ctypes.POINTER(OctreeFrame), vp, i64, ctypes.c_int, vp, vp]
         lib.asr_hip_point_normals.argtypes = [vp, vp, i64, vp, ctypes.c_int, vp, vp, vp]
         lib.asr_hip_normals_orient.argtypes = [vp, vp, vp, i64, vp, ctypes.c_int, vp, i64, vp, vp, ctypes.POINTER(i64)]
+        dp = ctypes.POINTER(ctypes.c_double)
+        lib.asr_hip_icp_step.argtypes = [vp, ctypes.POINTER(OctreeFrame), vp, i64, vp, vp, i64, dp, dp, ctypes.c_float,
+                                         ctypes.POINTER(IcpSums), vp]
+        lib.asr_hip_icp_update.argtypes = [ctypes.POINTER(IcpSums), dp, dp, dp]
+        lib.asr_hip_register_points.argtypes = [vp, ctypes.POINTER(OctreeFrame), vp, i64, vp, vp, i64,
+                                                ctypes.POINTER(IcpParams), dp, ctypes.POINTER(IcpReport)]
+        for name in ("asr_hip_icp_step", "asr_hip_icp_update", "asr_hip_register_points"):
+            getattr(lib, name).restype = ctypes.c_int
         for name in ("asr_hip_mesh_edges_count", "asr_hip_mesh_edges_fill", "asr_hip_mesh_topology", "asr_hip_mesh_smooth",
                      "asr_hip_mesh_fill_holes_count", "asr_hip_mesh_fill_holes_fill", "asr_hip_points_merge_count",
                      "asr_hip_points_merge_fill", "asr_hip_knn_index", "asr_hip_point_normals", "asr_hip_normals_orient"):

@@ -1164,6 +1164,159 @@ def orient_normals(points, normals, index=None, viewpoints=None, return_flips=Fa
     return res if len(res) > 1 else out
 
 
+ICP_MAX_ITERATIONS = 1000
+ICP_SUMS = ("ata", "atb", "sq_residual", "sq_distance", "pairs", "mode")
+ICP_REPORT = ("iterations", "converged", "degenerate", "pairs", "rmse", "fitness")
+
+
+def _transform12(transform, what="transform"):
+    """a rigid transform given as [3,4] or [4,4] (last row 0 0 0 1) -> 12 finite floats, the rows of (R | t)"""
+    import numpy as np
+    try:
+        t = np.array(transform.detach().cpu().numpy() if isinstance(transform, torch.Tensor) else transform,
+                     dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a 3x4 or 4x4 matrix" % what)
+    if t.shape == (4, 4):
+        if not np.array_equal(t[3], [0.0, 0.0, 0.0, 1.0]):
+            raise ValueError("the last row of a 4x4 %s must be 0 0 0 1" % what)
+        t = t[:3]
+    if t.shape != (3, 4):
+        raise ValueError("%s must be a 3x4 or 4x4 matrix" % what)
+    if not np.isfinite(t).all():
+        raise ValueError("%s is not finite" % what)
+    return t.copy()
+
+
+def icp_origin(frame):
+    """the centre of the frame's root cube in f64, the origin asr_hip_register_points linearises about:
+    (2^20 - offset[a]) * voxel_size[21]"""
+    return [float((1 << (_lib.ASR_MAX_LEVEL - 1)) - frame.offset[a]) * float(frame.voxel_size[_lib.ASR_MAX_LEVEL])
+            for a in range(3)]
+
+
+def check_register_arguments(target, target_normals, source, max_distance, init=None, max_iterations=50,
+                             rotation_tolerance=1e-7, translation_tolerance=0.0):
+    """the shapes and ranges of icp_step / register_points, or ValueError; no GPU involved
+    -> (n, m, the initial transform as a float64 [3,4] array)"""
+    import math
+    import numpy as np
+    shape = _shape(target)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError("target must have shape [N,3]")
+    n = shape[0]
+    if not 1 <= n < 2 ** 31:
+        raise ValueError("1 <= N < 2^31 target points are required")
+    if target_normals is not None and _shape(target_normals) != (n, 3):
+        raise ValueError("target_normals must have shape [N,3]")
+    shape = _shape(source)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError("source must have shape [M,3]")
+    m = shape[0]
+    if m >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 source points")
+    try:
+        cap = float(np.float32(max_distance))
+    except (TypeError, ValueError):
+        raise ValueError("max_distance must be a number")
+    if not (math.isfinite(cap) and cap > 0.0):
+        raise ValueError("max_distance must be finite and > 0 (as a float32)")
+    _check_int(max_iterations, 1, ICP_MAX_ITERATIONS, "max_iterations")
+    for name, tol in (("rotation_tolerance", rotation_tolerance), ("translation_tolerance", translation_tolerance)):
+        try:
+            good = float(tol) >= 0.0
+        except (TypeError, ValueError):
+            good = False
+        if not good:
+            raise ValueError("%s must be a number >= 0" % name)
+    t = _transform12(init, "init") if init is not None else np.hstack([np.eye(3), np.zeros((3, 1))])
+    return n, m, t
+
+
+def _doubles(values, count):
+    return (ctypes.c_double * count)(*[float(v) for v in values])
+
+
+def _sums_struct(sums):
+    if isinstance(sums, _lib.IcpSums):
+        return sums
+    s = _lib.IcpSums()
+    ata, atb = [float(v) for v in sums["ata"]], [float(v) for v in sums["atb"]]
+    if len(ata) != 21 or len(atb) != 6:
+        raise ValueError("sums: ata has 21 entries (upper triangle, row by row) and atb 6")
+    s.ata[:], s.atb[:] = ata, atb
+    s.sq_residual, s.sq_distance = float(sums["sq_residual"]), float(sums["sq_distance"])
+    s.pairs, s.mode = int(sums["pairs"]), int(sums["mode"])
+    return s
+
+
+def icp_step(frame, target, target_normals, source, transform, origin, max_distance, return_index=False):
+    """One ICP step (asr_hip_icp_step; the contract is in include/asr_hip.h): every source point, moved by `transform`
+    ([3,4] or [4,4], f64), is paired with its nearest target point within max_distance -- a brute-force search's result --
+    and the normal equations of the linearised alignment about `origin` are summed in f64, in a fixed order: point-to-plane
+    with target_normals, point-to-point with None.  -> dict(ata [21], atb [6], sq_residual, sq_distance, pairs, mode)
+    [, index int32 [M], -1 = no pair]"""
+    import numpy as np
+    n, m, _ = check_register_arguments(target, target_normals, source, max_distance)
+    t = _transform12(transform)
+    origin = [float(v) for v in np.asarray(origin, dtype=np.float64).reshape(3)]
+    if not all(np.isfinite(origin)):
+        raise ValueError("origin is not finite")
+    target = _dev(target, torch.float32)
+    normals = _dev(target_normals, torch.float32) if target_normals is not None else None
+    source = _dev(source, torch.float32)
+    dev = _same_device(target, normals, source)
+    index = torch.empty(m, dtype=torch.int32, device=dev) if return_index else None
+    sums = _lib.IcpSums()
+    context(dev).call("asr_hip_icp_step", ctypes.byref(frame), ptr(target), i64(n), ptr(normals), ptr(source), i64(m),
+                      _doubles(t.reshape(-1), 12), _doubles(origin, 3), ctypes.c_float(max_distance), ctypes.byref(sums),
+                      ptr(index))
+    out = {"ata": np.array(sums.ata[:]), "atb": np.array(sums.atb[:]), "sq_residual": sums.sq_residual,
+           "sq_distance": sums.sq_distance, "pairs": int(sums.pairs), "mode": int(sums.mode)}
+    return (out, index) if return_index else out
+
+
+def icp_update(sums, origin, transform):
+    """Solves a step's normal equations and applies the result (asr_hip_icp_update, host only, no GPU): A xi = -b by
+    Cholesky, xi = (omega, v), R <- Rw R, t <- Rw (t - o) + v + o.  `sums`: what icp_step returned (or a dict with the
+    same keys).  -> (transform f64 [3,4], xi f64 [6], degenerate bool); a degenerate system (too few pairs, a pivot at
+    rounding level) returns the transform as given and xi = 0."""
+    import numpy as np
+    t = _doubles(_transform12(transform).reshape(-1), 12)
+    xi = (ctypes.c_double * 6)()
+    rc = _lib.load().asr_hip_icp_update(ctypes.byref(_sums_struct(sums)), _doubles(np.asarray(origin).reshape(3), 3), t, xi)
+    if rc < 0:
+        raise AsrHipError("asr_hip_icp_update: null argument")
+    return np.array(t[:]).reshape(3, 4), np.array(xi[:]), rc == 1
+
+
+def register_points(frame, target, target_normals, source, max_distance, init=None, max_iterations=50,
+                    rotation_tolerance=1e-7, translation_tolerance=None):
+    """Rigid registration of `source` [M,3] onto `target` [N,3] by ICP (asr_hip_register_points): the target's index is
+    built once, every iteration is icp_step + icp_update about the centre of the frame's root cube (icp_origin), until an
+    update is within both tolerances (converged), the system is degenerate or max_iterations (1..1000) steps were taken.
+    Point-to-plane with target_normals, point-to-point with None.  translation_tolerance None: 1e-7 of the root cube's edge.
+    -> (transform f64 [3,4], dict(iterations, converged, degenerate, pairs, rmse, fitness))"""
+    import numpy as np
+    if translation_tolerance is None:
+        translation_tolerance = 1e-7 * float(frame.voxel_size[0])
+    n, m, t = check_register_arguments(target, target_normals, source, max_distance, init, max_iterations,
+                                       rotation_tolerance, translation_tolerance)
+    target = _dev(target, torch.float32)
+    normals = _dev(target_normals, torch.float32) if target_normals is not None else None
+    source = _dev(source, torch.float32)
+    dev = _same_device(target, normals, source)
+    params = _lib.IcpParams(float(max_distance), int(max_iterations), float(rotation_tolerance),
+                            float(translation_tolerance))
+    report = _lib.IcpReport()
+    tt = _doubles(t.reshape(-1), 12)
+    context(dev).call("asr_hip_register_points", ctypes.byref(frame), ptr(target), i64(n), ptr(normals), ptr(source),
+                      i64(m), ctypes.byref(params), tt, ctypes.byref(report))
+    out = {name: getattr(report, name) for name in ICP_REPORT}
+    out["converged"], out["degenerate"] = bool(out["converged"]), bool(out["degenerate"])
+    return np.array(tt[:]).reshape(3, 4), out
+
+
 def decode_mlp_at(code, shifts, w1, b1, w2, b2, w3, rows=None, voxel_sizes=None, gradient=False):
     """UNet5.decode(shifts, code[rows]) (net_definitions_torch.py:655-666) -> values [M,2]; with gradient=True
     (values, grad [M,3]) where grad is decode_with_gradient's d values[:,0] / d shift (:668-686, unscaled).

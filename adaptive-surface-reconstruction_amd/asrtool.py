@@ -7,6 +7,7 @@ reference (cpp/bin/main.cpp:114-177: `asrtool --in point_cloud.ply --out mesh.pl
                                                           [--thin SIZE] [--estimate-normals K [--viewpoint x,y,z]]
     python adaptive-surface-reconstruction_amd/asrtool.py --thin-cloud scan.ply out.ply --cell SIZE
     python adaptive-surface-reconstruction_amd/asrtool.py --orient-cloud raw.ply out.ply [--k K] [--viewpoint x,y,z]
+    python adaptive-surface-reconstruction_amd/asrtool.py --register source.ply target.ply out.ply [--max-distance D] [--iterations N] [--point-to-point]
     python adaptive-surface-reconstruction_amd/asrtool.py --compare mesh.ply reference.ply [--samples N] [--thresholds a,b,...] [--seed S]
     python adaptive-surface-reconstruction_amd/asrtool.py --decimate mesh.ply out.ply --cell SIZE
     python adaptive-surface-reconstruction_amd/asrtool.py --smooth-mesh mesh.ply out.ply [--iterations N] [--boundary free|pinned|along]
@@ -48,6 +49,14 @@ Options:
     --orient-cloud IN.ply OUT.ply [--k K]  Instead of reconstructing: writes the cloud with normals estimated as
               --estimate-normals K does (default 16), radii and colours carried over unchanged, points without a usable
               estimate dropped; prints one JSON line with the report (components, flipped, skipped, rounds, points, dropped)
+    --register SOURCE.ply TARGET.ply OUT.ply  Instead of reconstructing: aligns SOURCE to TARGET by ICP (a local method: the
+              two scans must overlap and be roughly aligned already) and writes the moved SOURCE, its normals rotated (zero
+              ones when it has none), radii and colours carried over unchanged; prints one JSON line with the report
+              (fitness, rmse, iterations, converged, degenerate, pairs, mode) and the 4x4 transform.  Point-to-plane when
+              TARGET has normals, else point-to-point (said on stderr)
+    --max-distance D  --register: pairs further apart than D are ignored (default: 5 % of TARGET's bounding-box diagonal)
+    --iterations N  --register: at most N iterations (default 50, 1 <= N <= 1000)
+    --point-to-point  --register: ignores TARGET's normals
     --thin-cloud IN.ply OUT.ply --cell SIZE  Instead of reconstructing: writes the cloud merged as --thin SIZE does, with its
               normals and, where the input has them, radii and colours; prints the cell size used
     --fill-mesh MESH.ply OUT.ply --max-edges N  Instead of reconstructing: closes the holes of at most N edges of an existing
@@ -270,6 +279,69 @@ def _orient_cloud(argv):
     return 0
 
 
+def _register(argv):
+    """--register SOURCE.ply TARGET.ply OUT.ply [--max-distance D] [--iterations N] [--point-to-point]: one JSON line, 0;
+    a message on stderr and 1 (before any GPU work) when something is wrong"""
+    import json
+    i = argv.index("--register")
+    paths = argv[i + 1:i + 4]
+    if len(paths) < 3 or any(p.startswith("--") for p in paths):
+        sys.stderr.write("asrtool: --register needs three files: SOURCE.ply TARGET.ply OUT.ply\n")
+        return 1
+    max_distance = None
+    if "--max-distance" in argv:
+        max_distance = _size(_option(argv, "--max-distance"))
+        if max_distance is None:
+            sys.stderr.write("asrtool: --register: --max-distance takes a positive number D\n")
+            return 1
+    iterations = 50
+    if "--iterations" in argv:
+        try:
+            iterations = int(_option(argv, "--iterations"))
+        except (TypeError, ValueError):
+            iterations = 0
+        if not 1 <= iterations <= 1000:
+            sys.stderr.write("asrtool: --register: --iterations takes a number N, 1 <= N <= 1000\n")
+            return 1
+    for p in paths[:2]:
+        if not os.path.isfile(p):
+            sys.stderr.write("asrtool: --register: no such file: %s\n" % p)
+            return 1
+    from asr_hip import ply
+    import numpy as np
+    clouds = []
+    for p in paths[:2]:
+        try:
+            clouds.append(ply.read_points(p, require_normals=False) + (ply.read_point_colors(p),))
+        except (ValueError, IndexError, OSError) as e:
+            sys.stderr.write("asrtool: --register: cannot read %s as a point cloud: %s\n" % (p, e))
+            return 1
+        if len(clouds[-1][0]) == 0:
+            sys.stderr.write("asrtool: --register: %s has no points\n" % p)
+            return 1
+    (source, source_normals, radii, colors), (target, target_normals, _, _) = clouds
+    if not np.isfinite(target).all():
+        sys.stderr.write("asrtool: --register: %s has points that are not finite\n" % paths[1])
+        return 1
+    has = lambda a: a is not None and len(a) == len(target)  # noqa: E731
+    plane = has(target_normals) and "--point-to-point" not in argv
+    if not plane and "--point-to-point" not in argv:
+        sys.stderr.write("asrtool: --register: %s has no normals, using point-to-point\n" % paths[1])
+    import adaptivesurfacereconstruction as asr
+    result = asr.register_points(source, target, target_normals if plane else None, max_distance=max_distance,
+                                 max_iterations=iterations)
+    transform = result.pop("transform")
+    if source_normals is not None and len(source_normals) == len(source):
+        moved, moved_normals = asr.transform_points(source, transform, source_normals)
+    else:
+        # (the cloud layout has nx ny nz: a source without normals gets zero ones)
+        moved, moved_normals = asr.transform_points(source, transform), np.zeros_like(source)
+    ply.write_points(paths[2], moved, moved_normals, radii if radii is not None and len(radii) else None, colors=colors)
+    print(json.dumps(dict(result, mode="point-to-plane" if plane else "point-to-point",
+                          transform=[[float(x) for x in row] for row in transform])))
+    return 0
+
+
 def _smooth_mesh(argv):
     """--smooth-mesh MESH.ply OUT.ply [--iterations N] [--boundary MODE]: 0, or a message on stderr and 1 (before any GPU
     work) when something is wrong"""
@@ -384,6 +456,8 @@ def main(argv=None):
         import adaptivesurfacereconstruction as asr
         print(asr.get_third_party_notices())
         return 0
+    if "--register" in argv:
+        return _register(argv)
     if "--compare" in argv:
         return _compare(argv)
     if "--decimate" in argv:

@@ -109,6 +109,9 @@ size_t asr_hip_struct_size(const char* name) {
     if (!strcmp(name, "asr_mesh_topology")) return sizeof(asr_mesh_topology);
     if (!strcmp(name, "asr_mesh_fill_report")) return sizeof(asr_mesh_fill_report);
     if (!strcmp(name, "asr_points_merge_report")) return sizeof(asr_points_merge_report);
+    if (!strcmp(name, "asr_icp_sums")) return sizeof(asr_icp_sums);
+    if (!strcmp(name, "asr_icp_params")) return sizeof(asr_icp_params);
+    if (!strcmp(name, "asr_icp_report")) return sizeof(asr_icp_report);
     return 0;
 }
 
@@ -716,6 +719,111 @@ int asr_hip_nearest_point(asr_hip_context* ctx, const asr_octree_frame* frame, c
     if (!frame || !points || (m > 0 && !queries)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "nearest_point: null argument");
     ctx->scratch.reset();
     return asr_geom_nearest(ctx, frame, points, n, queries, m, index_out, sqdist_out);
+}
+// the argument checks asr_hip_icp_step and asr_hip_register_points share; null on success, else the complaint
+static const char* icp_check(const asr_octree_frame* frame, const float* target, int64_t n, const float* source, int64_t m,
+                             const double transform[12], float max_distance) {
+    if (n < 1 || n >= (i64(1) << 31)) return "1 <= n < 2^31 target points are required";
+    if (m < 0 || m >= (i64(1) << 31)) return "0 <= m < 2^31 source points are required";
+    if (!frame || !target || (m > 0 && !source) || !transform) return "null argument";
+    if (!std::isfinite(max_distance) || !(max_distance > 0.f)) return "max_distance must be finite and > 0";
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(transform[i])) return "the transform is not finite";
+    return nullptr;
+}
+int asr_hip_icp_step(asr_hip_context* ctx, const asr_octree_frame* frame, const float* target, int64_t n,
+                     const float* target_normals, const float* source, int64_t m, const double transform[12],
+                     const double origin[3], float max_distance, asr_icp_sums* sums_out, int32_t* index_out) {
+    CTX_GUARD(ctx);
+    if (const char* bad = icp_check(frame, target, n, source, m, transform, max_distance))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "icp_step: %s", bad);
+    if (!origin || !sums_out) ASR_FAIL(ctx, ASR_HIP_EINVAL, "icp_step: null argument");
+    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "icp_step: the origin is not finite");
+    ctx->scratch.reset();
+    return asr_geom_icp_step(ctx, frame, target, n, target_normals, source, m, transform, origin, max_distance, sums_out,
+                             index_out);
+}
+int asr_hip_register_points(asr_hip_context* ctx, const asr_octree_frame* frame, const float* target, int64_t n,
+                            const float* target_normals, const float* source, int64_t m, const asr_icp_params* params,
+                            double transform_inout[12], asr_icp_report* report) {
+    CTX_GUARD(ctx);
+    if (!params || !report) ASR_FAIL(ctx, ASR_HIP_EINVAL, "register_points: null argument");
+    if (const char* bad = icp_check(frame, target, n, source, m, transform_inout, params->max_distance))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "register_points: %s", bad);
+    if (params->max_iterations < 1 || params->max_iterations > 1000)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "register_points: max_iterations %d is not in 1..1000", params->max_iterations);
+    if (!(params->rotation_tolerance >= 0.0) || !(params->translation_tolerance >= 0.0))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "register_points: the tolerances must be >= 0");
+    ctx->scratch.reset();
+    return asr_geom_register(ctx, frame, target, n, target_normals, source, m, params, transform_inout, report);
+}
+// Host only.  Cholesky A = L L^T on the full 6 x 6; a pivot (the diagonal entry before its square root) at or below
+// 2^-52 trace(A) means that A has no numerical rank 6: a planar target leaves three directions without any constraint.
+int asr_hip_icp_update(const asr_icp_sums* sums, const double origin[3], double transform_inout[12], double xi_out[6]) {
+    if (!sums || !origin || !transform_inout) return -1;
+    if (xi_out)
+        for (int i = 0; i < 6; ++i) xi_out[i] = 0.0;
+    if (sums->pairs < (sums->mode ? 6 : 3)) return 1;
+    double A[6][6], L[6][6] = {}, b[6], trace = 0.0;
+    for (int i = 0, k = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j, ++k) A[i][j] = A[j][i] = sums->ata[k];
+    for (int i = 0; i < 6; ++i) {
+        b[i] = sums->atb[i];
+        trace += A[i][i];
+        if (!std::isfinite(b[i])) return 1;
+        for (int j = 0; j < 6; ++j)
+            if (!std::isfinite(A[i][j])) return 1;
+    }
+    const double floor_pivot = 2.220446049250313e-16 * trace;  // 2^-52 trace(A)
+    for (int j = 0; j < 6; ++j) {
+        double d = A[j][j];
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        if (!(d > floor_pivot)) return 1;
+        L[j][j] = std::sqrt(d);
+        for (int i = j + 1; i < 6; ++i) {
+            double s = A[i][j];
+            for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+            L[i][j] = s / L[j][j];
+        }
+    }
+    double y[6], xi[6];
+    for (int i = 0; i < 6; ++i) {  // L y = -b
+        double s = -b[i];
+        for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
+        y[i] = s / L[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {  // L^T xi = y
+        double s = y[i];
+        for (int k = i + 1; k < 6; ++k) s -= L[k][i] * xi[k];
+        xi[i] = s / L[i][i];
+    }
+    for (int i = 0; i < 6; ++i)
+        if (!std::isfinite(xi[i])) return 1;
+    // Rodrigues: Rw = I + a K + c K^2 with K = [w]x, a = sin|w| / |w|, c = (1 - cos|w|) / |w|^2 = 2 sin^2(|w|/2) / |w|^2
+    const double wx = xi[0], wy = xi[1], wz = xi[2];
+    const double th = std::sqrt((wx * wx + wy * wy) + wz * wz);
+    double Rw[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    if (th >= 1e-300) {
+        const double a = std::sin(th) / th, h = std::sin(0.5 * th) / th, c = 2.0 * h * h;
+        const double K[3][3] = {{0, -wz, wy}, {wz, 0, -wx}, {-wy, wx, 0}};
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                const double k2 = (K[i][0] * K[0][j] + K[i][1] * K[1][j]) + K[i][2] * K[2][j];
+                Rw[i][j] = (Rw[i][j] + a * K[i][j]) + c * k2;
+            }
+    }
+    double T[12];
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j)
+            T[4 * i + j] = (Rw[i][0] * transform_inout[j] + Rw[i][1] * transform_inout[4 + j]) + Rw[i][2] * transform_inout[8 + j];
+        const double d0 = transform_inout[3] - origin[0], d1 = transform_inout[7] - origin[1],
+                     d2 = transform_inout[11] - origin[2];
+        T[4 * i + 3] = (((Rw[i][0] * d0 + Rw[i][1] * d1) + Rw[i][2] * d2) + xi[3 + i]) + origin[i];
+    }
+    memcpy(transform_inout, T, sizeof(T));
+    if (xi_out) memcpy(xi_out, xi, sizeof(xi));
+    return 0;
 }
 int asr_hip_mesh_sample(asr_hip_context* ctx, const float* vertices, int64_t num_vertices, const int32_t* triangles,
                         int64_t num_triangles, int64_t num_samples, uint64_t seed, float* points_out, float* normals_out,

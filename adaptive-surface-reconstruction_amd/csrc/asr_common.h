@@ -511,6 +511,13 @@ int asr_geom_knn(asr_hip_context* ctx, const asr_octree_frame* frame, const floa
 // nearest point of each query among pts (exact, ties to the smallest index); either output may be null
 int asr_geom_nearest(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, const float* queries,
                      i64 m, int32_t* index_out, float* sqdist_out);
+// one ICP step (pairs within max_distance, sums of the normal equations) and the ICP loop over one index of the target
+int asr_geom_icp_step(asr_hip_context* ctx, const asr_octree_frame* frame, const float* target, i64 n, const float* normals,
+                      const float* source, i64 m, const double transform[12], const double origin[3], float max_distance,
+                      asr_icp_sums* sums, int32_t* index_out);
+int asr_geom_register(asr_hip_context* ctx, const asr_octree_frame* frame, const float* target, i64 n, const float* normals,
+                      const float* source, i64 m, const asr_icp_params* params, double transform[12],
+                      asr_icp_report* report);
 // the k nearest points of every point, itself included, ordered by (squared distance, index); either output may be null
 int asr_geom_knn_index(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, int k,
                        int32_t* index_out, float* sqdist_out);

@@ -1986,6 +1986,249 @@ __global__ __launch_bounds__(256) void k_nearest(asr_octree_frame f, const float
 }
 
 // ------------------------------------------------------------------------------------------
+// One ICP step (asr_hip_icp_step): the transformed source points are the queries of k_nearest's search, capped at a
+// distance, and the terms of the normal equations are accumulated behind it.
+// Cap: only points with d2 <= cap2 count.  The level walk is k_nearest's with one more exit: a level is also final when
+// cap2 < g * g (g: the shrunk gap to the nearest inner face of the block).  Every point outside the block has a COMPUTED
+// squared distance of at least g * g -- the statement the existing exit "best < g * g" rests on, with the same rounding
+// margin of nearest_face_gap: the margin bounds what sqdist3 can lose against the true gap, whatever the value it is then
+// compared with -- so all of them are beyond the cap and the best of the block, if it is within the cap, is the best of
+// the cloud within the cap.  Unlike in k_nearest the test also runs on a level whose block is empty: a source point with no
+// counterpart leaves at the first level whose cells are wider than the cap instead of climbing to the whole cloud.
+// Sums: no float atomics.  The queries are taken in the Morton order of q; wave w owns the ICP_RUN consecutive queries
+// from w * ICP_RUN, lane t < 28 keeps entry t of (ata[21], atb[6], sq_residual) in a register across the run, lane 28
+// sq_distance, lane 29 the pair count.  The four waves of a block are added in wave order, k_icp_fold adds the blocks'
+// partials in a fixed order: the bits depend on the inputs alone.
+// ------------------------------------------------------------------------------------------
+struct IcpTransform {
+    double t[12];  // rows of (R | t)
+    double o[3];
+};
+constexpr int ICP_RUN = 32;     // queries per wave
+constexpr int ICP_TERMS = 30;   // 21 + 6 + 2 sums, the pair count
+constexpr int ICP_STRIDE = 32;  // doubles per partial
+constexpr int ICP_FOLD = 32;    // strided chains of k_icp_fold
+__global__ void k_icp_codes(asr_octree_frame f, IcpTransform x, const float* __restrict__ src, i64 m, float* __restrict__ q,
+                            u64* codes, int32_t* ids) {
+    const i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const float px = src[3 * i], py = src[3 * i + 1], pz = src[3 * i + 2];
+    float qx = __uint_as_float(0x7fc00000u), qy = qx, qz = qx;
+    if (finite3(px, py, pz)) {
+        qx = (float)(((x.t[0] * (double)px + x.t[1] * (double)py) + x.t[2] * (double)pz) + x.t[3]);
+        qy = (float)(((x.t[4] * (double)px + x.t[5] * (double)py) + x.t[6] * (double)pz) + x.t[7]);
+        qz = (float)(((x.t[8] * (double)px + x.t[9] * (double)py) + x.t[10] * (double)pz) + x.t[11]);
+    }
+    q[3 * i] = qx;
+    q[3 * i + 1] = qy;
+    q[3 * i + 2] = qz;
+    const float inv = f.inv_voxel_size[ASR_MAX_LEVEL];
+    u64 code = (u64(1) << 63) - 1;  // rows without a finite q last
+    if (finite3(qx, qy, qz))
+        code = asr_morton3d((u64)clamped_cell21(qx * inv, f.offset[0]), (u64)clamped_cell21(qy * inv, f.offset[1]),
+                            (u64)clamped_cell21(qz * inv, f.offset[2]));
+    codes[i] = code;
+    ids[i] = (int32_t)i;
+}
+// k_nearest's search of one finite query by one wave, capped: the smallest (squared distance bits << 32 | point index) of
+// the final level's block, the same value in every lane; ~0 when that block is empty
+__device__ inline u64 capped_nearest(const asr_octree_frame& f, const float4* __restrict__ sorted, const CellIndex& ci,
+                                     int lfine, int ldeep, float qx, float qy, float qz, float cap2, int lane, int* s_pref,
+                                     int* s_beg) {
+    const float inv = f.inv_voxel_size[ASR_MAX_LEVEL];
+    const int cx = clamped_cell21(qx * inv, f.offset[0]), cy = clamped_cell21(qy * inv, f.offset[1]),
+              cz = clamped_cell21(qz * inv, f.offset[2]);
+    int lev0 = lfine;
+    if (ldeep > lfine) {
+        const u64 code = asr_morton3d((u64)cx, (u64)cy, (u64)cz);
+        int b0, pop;
+        cell_range(ci, code >> (3 * (ASR_MAX_LEVEL - lfine)), lfine, b0, pop);
+        while (pop > KNN_CROWD && lev0 < ldeep) {
+            ++lev0;
+            cell_range(ci, code >> (3 * (ASR_MAX_LEVEL - lev0)), lev0, b0, pop);
+        }
+    }
+    u64 best = ~u64(0);
+    for (int lev = lev0; lev >= 0; --lev) {
+        const int s = ASR_MAX_LEVEL - lev, lim = (1 << lev) - 1;
+        const int x = cx >> s, y = cy >> s, z = cz >> s;
+        int b = 0, cnt = 0;
+        if (lane < 27) {
+            const int xx = x + lane % 3 - 1, yy = y + (lane / 3) % 3 - 1, zz = z + lane / 9 - 1;
+            if (xx >= 0 && yy >= 0 && zz >= 0 && xx <= lim && yy <= lim && zz <= lim)
+                cell_range(ci, asr_morton3d((u64)xx, (u64)yy, (u64)zz), lev, b, cnt);
+        }
+        int pre = cnt;
+#pragma unroll
+        for (int o = 1; o < 32; o <<= 1) {
+            const int up = __shfl_up(pre, o, 64);
+            if (lane >= o) pre += up;
+        }
+        const int total = __shfl(pre, 26, 64);
+        if (total > 0) {
+            __builtin_amdgcn_wave_barrier();
+            if (lane < 27) {
+                s_pref[lane + 1] = pre;
+                s_beg[lane] = b;
+            }
+            if (lane == 0) s_pref[0] = 0;
+            __builtin_amdgcn_wave_barrier();
+            for (int i0 = 0; i0 < total; i0 += 64) {
+                const int i = i0 + lane;
+                if (i < total) {
+                    const float4 pt = radius_candidate(sorted, s_pref, s_beg, i);
+                    const u64 key = ((u64)__float_as_uint(sqdist3(pt.x, pt.y, pt.z, qx, qy, qz)) << 32) |
+                                    (u64)(u32)__float_as_int(pt.w);
+                    best = key < best ? key : best;
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const u32 hi = __shfl_xor((u32)(best >> 32), o, 64), lo = __shfl_xor((u32)best, o, 64);
+                const u64 other = ((u64)hi << 32) | lo;
+                best = other < best ? other : best;
+            }
+        }
+        if (lev == 0) break;
+        const float g = fminf(fminf(nearest_face_gap(f, qx, x, lev, f.offset[0]), nearest_face_gap(f, qy, y, lev, f.offset[1])),
+                              nearest_face_gap(f, qz, z, lev, f.offset[2]));
+        // (an empty block has best = ~0, whose distance bits are a NaN: the first comparison is false)
+        if (g > 0.f && (__uint_as_float((u32)(best >> 32)) < g * g || cap2 < g * g)) break;
+    }
+    return best;
+}
+// the row (a, r) of one pair and one direction n: (e0..e5) = (u x n, n), e6 = r; d = u - v.  Named members and a chain of
+// selects: an array indexed by the lane's entry would be placed in LDS.
+struct IcpRow {
+    double e0, e1, e2, e3, e4, e5, e6;
+};
+__device__ inline IcpRow icp_row(double ux, double uy, double uz, double dx, double dy, double dz, double nx, double ny,
+                                 double nz) {
+    IcpRow e;
+    e.e0 = uy * nz - uz * ny;
+    e.e1 = uz * nx - ux * nz;
+    e.e2 = ux * ny - uy * nx;
+    e.e3 = nx;
+    e.e4 = ny;
+    e.e5 = nz;
+    e.e6 = (nx * dx + ny * dy) + nz * dz;
+    return e;
+}
+__device__ inline double icp_pick(const IcpRow& e, int k) {
+    return k == 0 ? e.e0 : k == 1 ? e.e1 : k == 2 ? e.e2 : k == 3 ? e.e3 : k == 4 ? e.e4 : k == 5 ? e.e5 : e.e6;
+}
+__device__ inline double icp_term(const IcpRow& e, int ti, int tj) { return icp_pick(e, ti) * icp_pick(e, tj); }
+template <bool PLANE>
+__global__ __launch_bounds__(256) void k_icp_pairs(asr_octree_frame f, const float4* __restrict__ sorted, CellIndex ci,
+                                                   int lfine, int ldeep, const float* __restrict__ q,
+                                                   const int32_t* __restrict__ order, i64 m,
+                                                   const float* __restrict__ target, const float* __restrict__ normals,
+                                                   double ox, double oy, double oz, float cap2, int32_t* index_out,
+                                                   double* __restrict__ partial) {
+    __shared__ int s_pref[4][28];
+    __shared__ int s_beg[4][28];
+    __shared__ double s_part[4][ICP_STRIDE];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // entry `lane` of the sums is e[ti] * e[tj]: the upper triangle of a a^T row by row, then a r, then r r
+    int ti = 6, tj = 6;
+    if (lane < 21) {
+        ti = 0;
+        int rem = lane;
+        while (rem >= 6 - ti) {
+            rem -= 6 - ti;
+            ++ti;
+        }
+        tj = ti + rem;
+    } else if (lane < 27) {
+        ti = lane - 21;
+    }
+    double acc = 0.0;
+    i64 pairs = 0;
+    const i64 first = (blockIdx.x * (i64)4 + wave) * ICP_RUN;
+    const i64 last = first + ICP_RUN < m ? first + ICP_RUN : m;
+    for (i64 w = first; w < last; ++w) {
+        const i64 j = order[w];
+        const float qx = q[3 * j], qy = q[3 * j + 1], qz = q[3 * j + 2];
+        int32_t hit = -1;
+        float yx = 0.f, yy = 0.f, yz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
+        if (finite3(qx, qy, qz)) {
+            const u64 best = capped_nearest(f, sorted, ci, lfine, ldeep, qx, qy, qz, cap2, lane, s_pref[wave], s_beg[wave]);
+            if (best != ~u64(0) && __uint_as_float((u32)(best >> 32)) <= cap2) {
+                hit = (int32_t)(u32)best;
+                yx = target[3 * (i64)hit];
+                yy = target[3 * (i64)hit + 1];
+                yz = target[3 * (i64)hit + 2];
+                if (PLANE) {
+                    nx = normals[3 * (i64)hit];
+                    ny = normals[3 * (i64)hit + 1];
+                    nz = normals[3 * (i64)hit + 2];
+                    if (!finite3(nx, ny, nz) || (nx == 0.f && ny == 0.f && nz == 0.f)) hit = -1;
+                }
+            }
+        }
+        if (lane == 0 && index_out) index_out[j] = hit;
+        if (hit < 0) continue;  // (the same decision in every lane)
+        ++pairs;
+        const double ux = (double)qx - ox, uy = (double)qy - oy, uz = (double)qz - oz;
+        const double vx = (double)yx - ox, vy = (double)yy - oy, vz = (double)yz - oz;
+        const double dx = ux - vx, dy = uy - vy, dz = uz - vz;
+        double term;
+        if (lane == 28) {
+            term = (dx * dx + dy * dy) + dz * dz;
+        } else if (PLANE) {
+            term = icp_term(icp_row(ux, uy, uz, dx, dy, dz, (double)nx, (double)ny, (double)nz), ti, tj);
+        } else {
+            const double t0 = icp_term(icp_row(ux, uy, uz, dx, dy, dz, 1.0, 0.0, 0.0), ti, tj);
+            const double t1 = icp_term(icp_row(ux, uy, uz, dx, dy, dz, 0.0, 1.0, 0.0), ti, tj);
+            const double t2 = icp_term(icp_row(ux, uy, uz, dx, dy, dz, 0.0, 0.0, 1.0), ti, tj);
+            term = (t0 + t1) + t2;
+        }
+        acc += term;
+    }
+    if (lane < ICP_TERMS) s_part[wave][lane] = lane == 29 ? __longlong_as_double(pairs) : acc;
+    __syncthreads();
+    if (wave == 0 && lane < ICP_TERMS) {
+        double out;
+        if (lane == 29)
+            out = __longlong_as_double(((__double_as_longlong(s_part[0][29]) + __double_as_longlong(s_part[1][29])) +
+                                        __double_as_longlong(s_part[2][29])) +
+                                       __double_as_longlong(s_part[3][29]));
+        else
+            out = ((s_part[0][lane] + s_part[1][lane]) + s_part[2][lane]) + s_part[3][lane];
+        partial[blockIdx.x * (i64)ICP_STRIDE + lane] = out;
+    }
+}
+// sums[t] = the partials of entry t: chain g of ICP_FOLD adds the blocks g, g + ICP_FOLD, ... in that order, then the chains
+// are added in order.  One block of 32 * ICP_FOLD threads; entry 29 (the pair count) is an integer.
+__global__ __launch_bounds__(32 * ICP_FOLD) void k_icp_fold(const double* __restrict__ partial, i64 nb, double* __restrict__ sums) {
+    __shared__ double s_chain[ICP_FOLD][32];
+    const int t = threadIdx.x & 31, g = threadIdx.x >> 5;
+    double acc = 0.0;
+    i64 cnt = 0;
+    if (t < ICP_TERMS)
+        for (i64 b = g; b < nb; b += ICP_FOLD) {
+            const double v = partial[b * ICP_STRIDE + t];
+            if (t == 29)
+                cnt += __double_as_longlong(v);
+            else
+                acc += v;
+        }
+    s_chain[g][t] = t == 29 ? __longlong_as_double(cnt) : acc;
+    __syncthreads();
+    if (g == 0 && t < ICP_TERMS) {
+        acc = 0.0;
+        cnt = 0;
+        for (int c = 0; c < ICP_FOLD; ++c) {
+            if (t == 29)
+                cnt += __double_as_longlong(s_chain[c][t]);
+            else
+                acc += s_chain[c][t];
+        }
+        sums[t] = t == 29 ? __longlong_as_double(cnt) : acc;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // Exact k-nearest-neighbour LISTS (asr_hip_knn_index): one wave per point in Morton order, the level walk of k_knn /
 // k_nearest.  The best 64 (squared distance bits << 32 | point index) keys seen on a level are one key per lane, ascending
 // over the lanes; row i of the output is the first k of them.  Candidates come 64 at a time: a batch in which no key lies
@@ -3613,6 +3856,105 @@ int asr_geom_nearest(asr_hip_context* ctx, const asr_octree_frame* frame, const 
     k_nearest<<<grid_for(m, 4), BLK, 0, ctx->stream>>>(*frame, st.sorted, st.index(), lfine, ldeep, queries, qids, m,
                                                        index_out, sqdist_out);
     ASR_CHECK_LAUNCH(ctx);
+    return ASR_HIP_OK;
+}
+
+// asr_hip_icp_step / asr_hip_register_points: asr_geom_nearest's index of the target, built once per call; per step the
+// transformed queries and their Morton order, one k_icp_pairs launch, k_icp_fold and the read-back of the sums.
+struct IcpIndex {
+    RadiusState st;
+    int lfine = 0, ldeep = 0;
+};
+static int icp_build_index(asr_hip_context* ctx, const asr_octree_frame* frame, const float* target, i64 n, IcpIndex& ix) {
+    ix.lfine = knn_fine_level(n);
+    ASR_TRY(build_point_index_grown(ctx, frame, target, n, 0, ix.lfine, ix.st, "icp: cell table overflow"));
+    ix.st.lhash = ix.lfine;
+    return deepen_crowded_index(ctx, target, ix.st, ix.lfine, &ix.ldeep);
+}
+static_assert(offsetof(asr_icp_sums, atb) == 21 * 8 && offsetof(asr_icp_sums, sq_residual) == 27 * 8 &&
+                      offsetof(asr_icp_sums, sq_distance) == 28 * 8 && offsetof(asr_icp_sums, pairs) == 29 * 8,
+              "k_icp_fold writes the sums in the struct's order");
+// one step on a built index; its temporaries are taken from the scratch arena and given back
+static int icp_step_indexed(asr_hip_context* ctx, const asr_octree_frame* frame, const IcpIndex& ix, const float* target,
+                            const float* normals, const float* source, i64 m, const double transform[12],
+                            const double origin[3], float max_distance, asr_icp_sums* sums, int32_t* index_out) {
+    memset(sums, 0, sizeof(*sums));
+    sums->mode = normals ? 1 : 0;
+    if (m <= 0) return ASR_HIP_OK;
+    ArenaMark mark;
+    arena_mark(ctx->scratch, mark);
+    const i64 nb = (m + 4 * ICP_RUN - 1) / (4 * ICP_RUN);
+    float* q = arena_alloc<float>(ctx->scratch, 3 * m);
+    u64* qcodes_u = arena_alloc<u64>(ctx->scratch, m);
+    u64* qcodes = arena_alloc<u64>(ctx->scratch, m);
+    int32_t* qids_u = arena_alloc<int32_t>(ctx->scratch, m);
+    int32_t* qids = arena_alloc<int32_t>(ctx->scratch, m);
+    double* partial = arena_alloc<double>(ctx->scratch, nb * ICP_STRIDE);
+    double* dsums = arena_alloc<double>(ctx->scratch, ICP_STRIDE);
+    if (!q || !qcodes_u || !qcodes || !qids_u || !qids || !partial || !dsums)
+        ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    IcpTransform x;
+    memcpy(x.t, transform, sizeof(x.t));
+    memcpy(x.o, origin, sizeof(x.o));
+    k_icp_codes<<<grid_for(m, BLK), BLK, 0, ctx->stream>>>(*frame, x, source, m, q, qcodes_u, qids_u);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_TRY((sort_pairs<u64, int32_t>(ctx, ctx->scratch, qcodes_u, qcodes, qids_u, qids, m, 63,
+                                      3 * (ASR_MAX_LEVEL - ix.lfine))));
+    const float cap2 = max_distance * max_distance;
+    if (normals)
+        k_icp_pairs<true><<<(unsigned)nb, BLK, 0, ctx->stream>>>(*frame, ix.st.sorted, ix.st.index(), ix.lfine, ix.ldeep, q,
+                                                                 qids, m, target, normals, x.o[0], x.o[1], x.o[2], cap2,
+                                                                 index_out, partial);
+    else
+        k_icp_pairs<false><<<(unsigned)nb, BLK, 0, ctx->stream>>>(*frame, ix.st.sorted, ix.st.index(), ix.lfine, ix.ldeep, q,
+                                                                  qids, m, target, nullptr, x.o[0], x.o[1], x.o[2], cap2,
+                                                                  index_out, partial);
+    ASR_CHECK_LAUNCH(ctx);
+    k_icp_fold<<<1, 32 * ICP_FOLD, 0, ctx->stream>>>(partial, nb, dsums);
+    ASR_CHECK_LAUNCH(ctx);
+    ASR_HIP_CHECK(ctx, hipMemcpyAsync(sums, dsums, ICP_TERMS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ASR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    arena_rewind(ctx->scratch, mark);
+    return ASR_HIP_OK;
+}
+int asr_geom_icp_step(asr_hip_context* ctx, const asr_octree_frame* frame, const float* target, i64 n, const float* normals,
+                      const float* source, i64 m, const double transform[12], const double origin[3], float max_distance,
+                      asr_icp_sums* sums, int32_t* index_out) {
+    ASR_TRY(ensure_flags(ctx));
+    IcpIndex ix;
+    if (m > 0) ASR_TRY(icp_build_index(ctx, frame, target, n, ix));
+    return icp_step_indexed(ctx, frame, ix, target, normals, source, m, transform, origin, max_distance, sums, index_out);
+}
+int asr_geom_register(asr_hip_context* ctx, const asr_octree_frame* frame, const float* target, i64 n, const float* normals,
+                      const float* source, i64 m, const asr_icp_params* params, double transform[12],
+                      asr_icp_report* report) {
+    ASR_TRY(ensure_flags(ctx));
+    IcpIndex ix;
+    if (m > 0) ASR_TRY(icp_build_index(ctx, frame, target, n, ix));
+    double origin[3];
+    for (int a = 0; a < 3; ++a)
+        origin[a] = (double)((1 << (ASR_MAX_LEVEL - 1)) - frame->offset[a]) * (double)frame->voxel_size[ASR_MAX_LEVEL];
+    memset(report, 0, sizeof(*report));
+    for (int it = 1; it <= params->max_iterations; ++it) {
+        asr_icp_sums sums;
+        ASR_TRY(icp_step_indexed(ctx, frame, ix, target, normals, source, m, transform, origin, params->max_distance, &sums,
+                                 nullptr));
+        report->iterations = it;
+        report->pairs = sums.pairs;
+        report->rmse = sums.pairs > 0 ? std::sqrt(sums.sq_distance / (double)sums.pairs) : 0.0;
+        report->fitness = m > 0 ? (double)sums.pairs / (double)m : 0.0;
+        double xi[6];
+        if (asr_hip_icp_update(&sums, origin, transform, xi) != 0) {
+            report->degenerate = 1;
+            break;
+        }
+        const double w = std::sqrt((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]);
+        const double v = std::sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
+        if (w <= params->rotation_tolerance && v <= params->translation_tolerance) {
+            report->converged = 1;
+            break;
+        }
+    }
     return ASR_HIP_OK;
 }
 

@@ -23,7 +23,7 @@
  *   context in between: the parked arrays then belong to that call.  Such calls are every _count of these pairs, both
  *   calls of the grid_neighbors and grid_coarsen pairs, the octree builds and the asr_hip_implicit_* entry points, and
  *   every single-call operator that needs device temporaries (the searches: knn_*, radius_neighbor_count,
- *   nearest_point, point_attributes_at; row_groups, invert_neighbors_list, sparse_conv_plan_create,
+ *   nearest_point, point_attributes_at, icp_step, register_points; row_groups, invert_neighbors_list, sparse_conv_plan_create,
  *   continuous_conv_f32; mesh_sample, mesh_topology, mesh_smooth; normals_orient).  Take every call that enqueues work
  *   on the context for one of them; the calls that only read or set host state (last_error, options, set_stream, ...)
  *   never are.  The input arrays of X_count must stay alive and unchanged until X_fill returns: fill reads them again.
@@ -750,6 +750,72 @@ int asr_hip_point_normals(asr_hip_context* ctx, const float* points_dev, int64_t
 int asr_hip_normals_orient(asr_hip_context* ctx, const float* points_dev, const float* normals_dev, int64_t n,
                            const int32_t* index_dev, int k, const float* viewpoints_dev, int64_t num_viewpoints,
                            float* normals_out_dev, uint8_t* flips_out_dev, int64_t report[4]);
+
+/* ---- rigid registration of two scans: point-to-plane / point-to-point ICP (not in the reference) ------ */
+/* Sums of one linearised step.  ata: the upper triangle of the 6 x 6 normal matrix, row by row ((0,0) (0,1) .. (0,5)
+ * (1,1) .. (5,5)); atb: its right-hand side; unknowns xi = (omega, v): a small rotation about `origin` and a translation.
+ * mode: 1 = point-to-plane, 0 = point-to-point (three rows per pair); set by asr_hip_icp_step, read by _update. */
+typedef struct asr_icp_sums {
+    double ata[21];
+    double atb[6];
+    double sq_residual; /* sum of r^2 over all rows                     */
+    double sq_distance; /* sum of |q - y|^2 over all pairs              */
+    int64_t pairs;
+    int32_t mode;
+    int32_t reserved;
+} asr_icp_sums;
+typedef struct asr_icp_params {
+    float max_distance;           /* the cap on a pair's distance: finite, > 0                        */
+    int max_iterations;           /* 1..1000                                                          */
+    double rotation_tolerance;    /* stop when |omega| <= this (radians) ...                          */
+    double translation_tolerance; /* ... and |v| <= this; both >= 0                                   */
+} asr_icp_params;
+typedef struct asr_icp_report {
+    int iterations; /* steps evaluated                                                                */
+    int converged;  /* the last update was within both tolerances                                     */
+    int degenerate; /* the last step's normal equations had no unique solution; the transform is that
+                       of the step before                                                             */
+    int64_t pairs;  /* of the LAST evaluated step, like rmse = sqrt(sq_distance / pairs) (0 without
+                       pairs) and fitness = pairs / m (0 for m = 0)                                   */
+    double rmse;
+    double fitness;
+} asr_icp_report;
+/* One ICP step: pairs every source point with its nearest target point within max_distance and accumulates the normal
+ * equations of the linearised alignment.  target_dev f32 [n,3], target_normals_dev f32 [n,3] or NULL (point-to-point),
+ * source_dev f32 [m,3]; transform: 12 doubles, the rows (R | t) of a 3 x 4; origin: 3 doubles.  The frame has the role it
+ * has for asr_hip_nearest_point: it only defines the acceleration grid of the TARGET.  Per source point p:
+ *   q   = (float)(((R00 (double)px + R01 (double)py) + R02 (double)pz) + t0), qy and qz alike: f64, uncontracted, rounded once;
+ *   y   = the target point that minimises d2 = ((dx dx + dy dy) + dz dz) in f32 (asr_hip_nearest_point's arithmetic) among
+ *         those with d2 <= cap2 = max_distance * max_distance (f32); ties go to the smallest index: the result of a brute-
+ *         force search with that restriction;
+ *   no pair (index -1) when p or q is not finite, when no target point is within the cap, or, with normals, when the normal
+ *         of y has a non-finite component or is (0,0,0);
+ *   terms, f64 from the f32 values: u = q - o, v = y - o, n = the normal of y as given (not normalised),
+ *         a = (u x n, n), r = (nx (ux-vx) + ny (uy-vy)) + nz (uz-vz); a pair adds a a^T to ata, a r to atb, r^2 to sq_residual
+ *         and ((ux-vx)^2 + (uy-vy)^2) + (uz-vz)^2 to sq_distance.  Point-to-point: the three rows n = e_0, e_1, e_2 of a pair
+ *         are added up in that order first (r_k = u_k - v_k; sq_residual == sq_distance).
+ * The sums are added in a fixed order (queries in the Morton order of q, a fixed run per wave, partials folded in index
+ * order; no float atomics): the same bits on every run and on a fresh context.  index_out_dev (int32 [m]) may be NULL.
+ * ASR_HIP_EINVAL: sizes and non-finite target points as for asr_hip_nearest_point; max_distance not finite or <= 0; a non-
+ * finite transform or origin.  m = 0 is valid and gives zero sums.  The index build reads its cell counts back, the sums
+ * are the one read-back of the step itself. */
+int asr_hip_icp_step(asr_hip_context* ctx, const asr_octree_frame* frame, const float* target_dev, int64_t n,
+                     const float* target_normals_dev, const float* source_dev, int64_t m, const double transform[12],
+                     const double origin[3], float max_distance, asr_icp_sums* sums_out, int32_t* index_out_dev);
+/* Host only, no context: solves A xi = -b (A, b: ata, atb) by Cholesky in f64 and applies xi = (omega, v):
+ *     R <- Rw R,   t <- Rw (t - o) + v + o,   Rw = I + sin|w|/|w| [w]x + (1 - cos|w|)/|w|^2 [w]x^2   (I for |w| < 1e-300).
+ * xi_out (6 doubles) may be NULL.  Returns 0, or 1 = degenerate, with transform_inout untouched and xi_out zero: fewer
+ * than 6 (mode 1) or 3 (mode 0) pairs, a non-finite sum, or a pivot <= 2^-52 trace(A); -1 for a NULL argument. */
+int asr_hip_icp_update(const asr_icp_sums* sums, const double origin[3], double transform_inout[12], double xi_out[6]);
+/* The ICP loop: the target's point index is built once; each iteration is asr_hip_icp_step at the current transform, its
+ * read-back, asr_hip_icp_update and the stop test -- converged when |omega| <= rotation_tolerance and |v| <=
+ * translation_tolerance after the update was applied, degenerate when the update says so -- at most max_iterations times.
+ * origin[a] = (double)(2^20 - frame.offset[a]) * (double)frame.voxel_size[21], the centre of the frame's root cube.
+ * The queries are sorted again in every iteration: the result is a pure function of the arguments.  ASR_HIP_EINVAL as for
+ * asr_hip_icp_step, for max_iterations outside 1..1000 and tolerances that are negative or NaN. */
+int asr_hip_register_points(asr_hip_context* ctx, const asr_octree_frame* frame, const float* target_dev, int64_t n,
+                            const float* target_normals_dev, const float* source_dev, int64_t m,
+                            const asr_icp_params* params, double transform_inout[12], asr_icp_report* report);
 /* (asr_hip_implicit_query, the whole-path query on the last forward, is declared after asr_hip_implicit_stage_ms) */
 
 /* ---- whole path: the section of asr::ReconstructSurface between the pre-filter and the
