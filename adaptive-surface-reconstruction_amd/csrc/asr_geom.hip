@@ -886,36 +886,65 @@ __device__ inline void cell_range(const CellIndex& ci, u64 cell, int lev, int& b
     cnt = lo2 - lo;
 }
 
+// Prefix / begin tables of the point ranges [b, b + n) that lanes 0..NCELL-1 hold; returns the candidate total.
+// WALK: the form for a caller that goes through several blocks in a loop (the level walk below).  A total below `need`
+// is returned with the tables untouched -- the caller skips such a block -- and a wave barrier comes BEFORE the writes
+// too: the previous block's reads of the tables are finished.
 template <int NCELL>
-__device__ inline int cells_prefix(int b, int n, int lane, int* s_pref, int* s_beg) {
-    int pre = n;  // inclusive prefix of n over lanes 0..NCELL-1
+__device__ inline int cells_inclusive(int n, int lane) {  // inclusive prefix of n over lanes 0..NCELL-1
+    int pre = n;
 #pragma unroll
     for (int o = 1; o < (NCELL > 32 ? 64 : 32); o <<= 1) {
         int up = __shfl_up(pre, o, 64);
         if (lane >= o) pre += up;
+    }
+    return pre;
+}
+template <int NCELL, bool WALK = false>
+__device__ inline int cells_prefix(int b, int n, int lane, int* s_pref, int* s_beg, int need = 0) {
+    const int pre = cells_inclusive<NCELL>(n, lane);
+    int total = 0;
+    if (WALK) {
+        total = __shfl(pre, NCELL - 1, 64);
+        if (total < need) return total;
+        __builtin_amdgcn_wave_barrier();
     }
     if (lane < NCELL) {
         s_pref[lane + 1] = pre;
         s_beg[lane] = b;
     }
     if (lane == 0) s_pref[0] = 0;
-    const int total = __shfl(pre, NCELL - 1, 64);
+    if (!WALK) total = __shfl(pre, NCELL - 1, 64);
     __builtin_amdgcn_wave_barrier();
     return total;
+}
+// THE 3^3 look-up: lane c < 27 gets the point range [b, b + n) of cell (x, y, z) + (c % 3, c / 3 % 3, c / 9) - 1 of level
+// `lev`; cells outside the root cube and the lanes from 27 up get n = 0.
+__device__ inline void block27_ranges(const CellIndex& ci, int x, int y, int z, int lev, int lane, int& b, int& n) {
+    const int lim = (1 << lev) - 1;
+    b = 0;
+    n = 0;
+    if (lane < 27) {
+        const int xx = x + lane % 3 - 1, yy = y + (lane / 3) % 3 - 1, zz = z + lane / 9 - 1;
+        if (xx >= 0 && yy >= 0 && zz >= 0 && xx <= lim && yy <= lim && zz <= lim)
+            cell_range(ci, asr_morton3d((u64)xx, (u64)yy, (u64)zz), lev, b, n);
+    }
+}
+// ... and its tables.  The barrier a level loop needs before the writes is in the helper (cells_prefix, WALK), not at the
+// call sites.
+template <bool WALK = false>
+__device__ inline int block27_cells(const CellIndex& ci, int x, int y, int z, int lev, int lane, int* s_pref, int* s_beg,
+                                    int need = 0) {
+    int b, n;
+    block27_ranges(ci, x, y, z, lev, lane, b, n);
+    return cells_prefix<27, WALK>(b, n, lane, s_pref, s_beg, need);
 }
 __device__ inline int radius_cells(const asr_octree_frame& f, const CellIndex& ci, float cx, float cy, float cz,
                                    float r, int lane, int* s_pref, int* s_beg) {
     const int lev = query_level(f, r);
     int x, y, z;
     frame_coord(f, cx, cy, cz, lev, x, y, z);
-    const int lim = (1 << lev) - 1;
-    int b = 0, n = 0;
-    if (lane < 27) {
-        int xx = x + lane % 3 - 1, yy = y + (lane / 3) % 3 - 1, zz = z + lane / 9 - 1;
-        if (xx >= 0 && yy >= 0 && zz >= 0 && xx <= lim && yy <= lim && zz <= lim)
-            cell_range(ci, asr_morton3d((u64)xx, (u64)yy, (u64)zz), lev, b, n);
-    }
-    return cells_prefix<27>(b, n, lane, s_pref, s_beg);
+    return block27_cells(ci, x, y, z, lev, lane, s_pref, s_beg);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -947,11 +976,8 @@ __device__ inline int aligned_cells(const CellIndex& ci, const AlignedQ& aq, u64
         const int xx = 2 * x - 1 + (lane & 3), yy = 2 * y - 1 + ((lane >> 2) & 3), zz = 2 * z - 1 + (lane >> 4);
         if (xx >= 0 && yy >= 0 && zz >= 0 && xx <= lim && yy <= lim && zz <= lim)
             cell_range(ci, asr_morton3d((u64)xx, (u64)yy, (u64)zz), lev + 1, b, n);
-    } else if (lane < 27) {
-        const int lim = (1 << lev) - 1;
-        const int xx = x + lane % 3 - 1, yy = y + (lane / 3) % 3 - 1, zz = z + lane / 9 - 1;
-        if (xx >= 0 && yy >= 0 && zz >= 0 && xx <= lim && yy <= lim && zz <= lim)
-            cell_range(ci, asr_morton3d((u64)xx, (u64)yy, (u64)zz), lev, b, n);
+    } else {
+        block27_ranges(ci, x, y, z, lev, lane, b, n);
     }
     return cells_prefix<64>(b, n, lane, s_pref, s_beg);
 }
@@ -1458,13 +1484,149 @@ __global__ void k_radius_unpack_heavy(const u64* keys, const int32_t* hrow, i64 
         compat[o] = ratio * ratio;
     }
 }
-// Exact k-th nearest neighbour distance, one wave per point (in Morton order).  Level by level,
-// finest first: lanes 0..26 look up the 3^3 cells around the point's cell; if they hold >= k points
-// the k-th smallest squared distance d_k among them is selected; it is exact as soon as
-// d_k <= (cell size)^2, because every point closer than one cell size lies inside the 3^3 block.
+// ------------------------------------------------------------------------------------------
+// THE LEVEL WALK of the nearest-neighbour searches (k_knn, k_nearest, k_icp_pairs, k_knn_index): one wave per query,
+// level by level from a start level towards the root, until a level's result is provably that of the whole cloud.
+// Written once: nearest_walk<CAPPED> below is k_nearest's and k_icp_pairs' search.  k_knn and k_knn_index share the
+//   look-up (block27_ranges) and this description; their start level, prefix and face test stay written out in the
+//   kernels, in the order they had: with the helpers (crowded_start_level, cells_prefix, block_face_gap, candidate_key)
+//   the two compiled to other schedules, measured 0.4 % (knn_index) and 1.5 % (knn_radius) slower, and written out
+//   they compile to the instructions they had before the look-up was shared.
+// Block: on level `lev` lanes 0..26 look up the 3^3 cells around the query's cell (block27_ranges; a block with too few
+//   points for the caller is skipped before its tables are written) and the wave walks the block's points 64 at a
+//   time (radius_candidate).  Results are (squared distance bits << 32 | point index) keys, so ties go to the smallest
+//   index.  A query outside the root cube is clamped into a boundary cell; the block of level 0 is the whole cloud.
+// Crowding start (crowded_start_level): the walk starts on the finest table level lfine, or -- in a cloud with dense
+//   spots, whose codes are sorted down to ldeep > lfine -- on the level at which the query's own cell holds at most
+//   KNN_CROWD points; cells below lfine are found by binary search in the sorted codes (cell_range).
+// Face gap (block_face_gap): a point that is NOT in the block lies beyond one of the block's six faces, so it is at least
+//   as far away as that face; faces on the root cube's boundary do not count (points beyond them were clamped into the
+//   boundary cells, which the block holds).  g is the distance to the nearest counting face, shrunk by the rounding
+//   margin, and the statement every exit rests on is: every point outside the block has a COMPUTED squared distance of at
+//   least g * g.  Margin: a point is binned by floor(fl(p * inv)) and the face position is computed as
+//   fl(fl(c) * voxel_size), where inv * voxel_size = 1 +- 2^-23.  A point beyond the face at integer coordinate c has
+//   p < F + |F| 2^-23 with F = c / inv, the computed face f is within |F| 2^-22 of F, and sqdist3 loses at most 2^-22
+//   relative: the gap q - f is shrunk to (q - f)(1 - 2^-20) - |f| 2^-20, which covers all of it several times over.  The
+//   margin bounds what sqdist3 can lose against the true gap, whatever value g * g is then compared with.
+// Exits: nearest_walk leaves when its best key has d2 < g * g.  On an empty block (best = ~0, whose distance bits are a
+//   NaN: the comparison would be false) it moves on at once.  CAPPED (only points with d2 <= cap2 count) adds the exit
+//   cap2 < g * g: all points outside the block are then beyond the cap, so the best of the block, if it is within the cap,
+//   is the best of the cloud within the cap -- and a query with no counterpart leaves at the first level whose cells are
+//   wider than the cap instead of climbing to the whole cloud.  k_knn_index puts its k-th key in place of the best; the
+//   test d2_k < g * g is strict, so a point outside the block cannot even tie with the k-th key and no smaller index is
+//   lost at the block's boundary.  k_knn (distances only, queries are points of the cloud, hence inside their centre
+//   cell) keeps its own exit d_k <= (cell size)^2.
+// ------------------------------------------------------------------------------------------
+constexpr int KNN_CROWD = 1024;  // points of a finest-level cell above which a point starts its search on a finer level
+__device__ inline int crowded_start_level(const CellIndex& ci, u64 code, int lfine, int ldeep) {
+    int lev0 = lfine;
+    if (ldeep > lfine) {
+        int b0, pop;
+        cell_range(ci, code >> (3 * (ASR_MAX_LEVEL - lfine)), lfine, b0, pop);
+        while (pop > KNN_CROWD && lev0 < ldeep) {
+            ++lev0;
+            cell_range(ci, code >> (3 * (ASR_MAX_LEVEL - lev0)), lev0, b0, pop);
+        }
+    }
+    return lev0;
+}
+// floor(t) + off clamped into [0, 2^21): k_point_codes' cell for points of the cube, the nearest boundary cell outside
+__device__ inline int clamped_cell21(float t, int off) {
+    const float ft = fminf(fmaxf(floorf(t), -4.0e9f), 4.0e9f);
+    const i64 c = (i64)ft + off, lim = (1 << ASR_MAX_LEVEL) - 1;
+    return (int)(c < 0 ? 0 : c > lim ? lim : c);
+}
+// the level-21 cell of a finite query
+__device__ inline void query_cell21(const asr_octree_frame& f, float qx, float qy, float qz, int& cx, int& cy, int& cz) {
+    const float inv = f.inv_voxel_size[ASR_MAX_LEVEL];
+    cx = clamped_cell21(qx * inv, f.offset[0]);
+    cy = clamped_cell21(qy * inv, f.offset[1]);
+    cz = clamped_cell21(qz * inv, f.offset[2]);
+}
+__device__ inline bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+// Morton code of a query's level-21 cell, the sort key of the query order; non-finite rows last
+__device__ inline u64 query_code21(const asr_octree_frame& f, float qx, float qy, float qz) {
+    if (!finite3(qx, qy, qz)) return (u64(1) << 63) - 1;
+    int cx, cy, cz;
+    query_cell21(f, qx, qy, qz, cx, cy, cz);
+    return asr_morton3d((u64)cx, (u64)cy, (u64)cz);
+}
+// distance from q to the nearer of the block's two faces on one axis, shrunk by the rounding margin; +inf for a face
+// on the root cube's boundary, negative when q lies outside the block.  c = centre cell of the block on `lev`.
+__device__ inline float nearest_face_gap(const asr_octree_frame& f, float q, int c, int lev, int off) {
+    const int s = ASR_MAX_LEVEL - lev;
+    const float vs = f.voxel_size[ASR_MAX_LEVEL];
+    const float keep = 0.99999904632568359375f, slack = 9.5367431640625e-7f;  // 1 - 2^-20, 2^-20
+    float g = __uint_as_float(0x7f800000u);
+    if (c - 1 > 0) {
+        const float face = (float)(((i64)(c - 1) << s) - off) * vs;
+        g = fminf(g, (q - face) * keep - fabsf(face) * slack);
+    }
+    if (c + 2 < (1 << lev)) {
+        const float face = (float)(((i64)(c + 2) << s) - off) * vs;
+        g = fminf(g, (face - q) * keep - fabsf(face) * slack);
+    }
+    return g;
+}
+// g of the block around cell (x, y, z) of level `lev`
+__device__ inline float block_face_gap(const asr_octree_frame& f, float qx, float qy, float qz, int x, int y, int z, int lev) {
+    return fminf(fminf(nearest_face_gap(f, qx, x, lev, f.offset[0]), nearest_face_gap(f, qy, y, lev, f.offset[1])),
+                 nearest_face_gap(f, qz, z, lev, f.offset[2]));
+}
+__device__ inline u64 shfl_xor_u64(u64 v, int o) {
+    const u32 hi = __shfl_xor((u32)(v >> 32), o, 64), lo = __shfl_xor((u32)v, o, 64);
+    return ((u64)hi << 32) | lo;
+}
+__device__ inline u64 shfl_u64(u64 v, int src) {
+    const u32 hi = __shfl((u32)(v >> 32), src, 64), lo = __shfl((u32)v, src, 64);
+    return ((u64)hi << 32) | lo;
+}
+// (squared distance bits << 32) | original point index of candidate pt for the query (qx, qy, qz)
+__device__ inline u64 candidate_key(const float4& pt, float qx, float qy, float qz) {
+    return ((u64)__float_as_uint(sqdist3(pt.x, pt.y, pt.z, qx, qy, qz)) << 32) | (u64)(u32)__float_as_int(pt.w);
+}
+// The walk for ONE nearest point of one finite query by one wave: the smallest key of the final level's block, the same
+// value in every lane; ~0 when that block is empty (CAPPED only: level 0 holds all n >= 1 points).
+template <bool CAPPED>
+__device__ __forceinline__ u64 nearest_walk(const asr_octree_frame& f, const float4* __restrict__ sorted,
+                                            const CellIndex& ci, int lfine, int ldeep, float qx, float qy, float qz,
+                                            float cap2, int lane, int* s_pref, int* s_beg) {
+    int cx, cy, cz;
+    query_cell21(f, qx, qy, qz, cx, cy, cz);
+    const int lev0 = crowded_start_level(ci, asr_morton3d((u64)cx, (u64)cy, (u64)cz), lfine, ldeep);
+    u64 best = ~u64(0);
+    for (int lev = lev0; lev >= 0; --lev) {
+        const int s = ASR_MAX_LEVEL - lev;
+        const int x = cx >> s, y = cy >> s, z = cz >> s;
+        const int total = block27_cells<true>(ci, x, y, z, lev, lane, s_pref, s_beg, 1);
+        if (!CAPPED && total == 0) continue;  // only the cap can end the walk on an empty block
+        if (total > 0) {
+            for (int i0 = 0; i0 < total; i0 += 64) {
+                const int i = i0 + lane;
+                if (i < total) {
+                    const u64 key = candidate_key(radius_candidate(sorted, s_pref, s_beg, i), qx, qy, qz);
+                    best = key < best ? key : best;
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const u64 other = shfl_xor_u64(best, o);
+                best = other < best ? other : best;
+            }
+        }
+        if (lev == 0) break;
+        const float g = block_face_gap(f, qx, qy, qz, x, y, z, lev);
+        if (g > 0.f && (__uint_as_float((u32)(best >> 32)) < g * g || (CAPPED && cap2 < g * g))) break;
+    }
+    return best;
+}
+
+// Exact k-th nearest neighbour distance, one wave per point (in Morton order): the level walk above with the query's cell
+// taken from frame_coord (from the sorted codes below lfine).  If a block holds >= k points the k-th smallest squared
+// distance d_k among them is selected; it is exact as soon as d_k <= (cell size)^2, because every point closer than one
+// cell size lies inside the 3^3 block.
 // Selection: binary search on the bit pattern of the (non-negative) squared distances with wave
 // ballots; up to 512 candidates are held in registers, larger sets are streamed from memory.
-constexpr int KNN_CROWD = 1024;  // points of a finest-level cell above which a point starts its search on a finer level
 __global__ __launch_bounds__(256) void k_knn(asr_octree_frame f, const float4* sorted, i64 n, CellIndex ci, int lfine,
                                              int ldeep, int k, const float* radii_in, float radius_fraction,
                                              int outlier_threshold, float* radii_out,
@@ -1511,12 +1673,8 @@ __global__ __launch_bounds__(256) void k_knn(asr_octree_frame f, const float4* s
         x = min(max(x, 0), lim);  // points outside the root cube were clamped into it
         y = min(max(y, 0), lim);
         z = min(max(z, 0), lim);
-        int b = 0, cnt = 0;
-        if (lane < 27) {
-            int xx = x + lane % 3 - 1, yy = y + (lane / 3) % 3 - 1, zz = z + lane / 9 - 1;
-            if (xx >= 0 && yy >= 0 && zz >= 0 && xx <= lim && yy <= lim && zz <= lim)
-                cell_range(ci, asr_morton3d((u64)xx, (u64)yy, (u64)zz), lev, b, cnt);
-        }
+        int b, cnt;
+        block27_ranges(ci, x, y, z, lev, lane, b, cnt);
         int pre = cnt;
 #pragma unroll
         for (int o = 1; o < 32; o <<= 1) {
@@ -1699,7 +1857,6 @@ __global__ __launch_bounds__(256) void k_knn(asr_octree_frame f, const float4* s
     if (lane == 0 && radii_out) radii_out[__float_as_int(me.w)] = sqrtf(__uint_as_float(kth_bits));
 }
 
-
 // ------------------------------------------------------------------------------------------
 // kNN radius, fast path: ONE WAVE PER OCCUPIED CELL of the finest level.  All points of a cell share the 3^3
 // block of candidate cells, so the wave stages the candidates in LDS 64 at a time and every lane keeps the K
@@ -1779,8 +1936,9 @@ __global__ __launch_bounds__(256) void k_knn_cells(asr_octree_frame f, const flo
     z = min(max(z, 0), lim);
     int b = 0, cnt = 0;
     if (lane < 27) {
-        // candidate cells nearest first (the cell itself, 6 face, 12 edge, 8 corner neighbours): the k-th distance is
-        // tight after the first few, and chunks of the far cells are skipped by the ballot test below
+        // Not block27_cells: the candidate cells come nearest first (the cell itself, 6 face, 12 edge, 8 corner
+        // neighbours) -- the k-th distance is tight after the first few, and chunks of the far cells are skipped by the
+        // ballot test below -- and lfine is a table level, so the table is probed directly.
         constexpr unsigned char order[27] = {13, 4, 10, 12, 14, 16, 22, 1, 3, 5, 7, 9, 11, 15, 17, 19, 21, 23, 25,
                                              0, 2, 6, 8, 18, 20, 24, 26};
         const int c = order[lane];
@@ -1793,12 +1951,9 @@ __global__ __launch_bounds__(256) void k_knn_cells(asr_octree_frame f, const flo
             }
         }
     }
-    int pre = cnt;
-#pragma unroll
-    for (int o = 1; o < 32; o <<= 1) {
-        int up = __shfl_up(pre, o, 64);
-        if (lane >= o) pre += up;
-    }
+    // The prefix is cells_prefix's; the total and the tables are written out in this order: through cells_prefix the
+    // tables cost two LDS writes under a branch instead of one paired write, and knn_radius was 1.5 % slower.
+    const int pre = cells_inclusive<27>(cnt, lane);
     const int total = __shfl(pre, 26, 64);
     const int qb = __shfl(b, 0, 64), qn = __shfl(cnt, 0, 64);  // the cell itself: its points are the queries
     if (lane < 27) {
@@ -1852,54 +2007,13 @@ __global__ __launch_bounds__(256) void k_knn_cells(asr_octree_frame f, const flo
 
 // ------------------------------------------------------------------------------------------
 // Nearest point of ANOTHER set (asr_hip_nearest_point): one wave per query, queries taken in Morton order so that
-// neighbouring waves probe the same cells.  Level by level, finest first, like k_knn: lanes 0..26 look up the 3^3 block
-// around the query's cell, the wave walks the block's points 64 at a time and keeps the smallest (squared distance
-// bits, point index) key -- ties go to the smallest index.
-// A query need not lie in the centre cell of its block (one outside the root cube was clamped into a boundary cell), so
-// k_knn's "d <= (cell size)^2" does not apply.  What holds for every query: a point that is NOT in the block lies beyond
-// one of the block's six faces, so it is at least as far away as that face.  The result of a level is exact when it is
-// closer than the nearest face; faces on the root cube's boundary do not count (points beyond them were clamped into
-// the boundary cells, which the block holds).  Level 0 is the whole cloud.
-// Rounding: a point is binned by floor(fl(p * inv)) and the face position is computed as fl(fl(c) * voxel_size), where
-// inv * voxel_size = 1 +- 2^-23.  A point beyond the face at integer coordinate c has p < F + |F| 2^-23 with F = c / inv,
-// the computed face f is within |F| 2^-22 of F, and sqdist3 loses at most 2^-22 relative: the gap q - f is shrunk to
-// (q - f)(1 - 2^-20) - |f| 2^-20, which covers all of it several times over.
+// neighbouring waves probe the same cells; nearest_walk without a cap.
 // ------------------------------------------------------------------------------------------
-// floor(t) + off clamped into [0, 2^21): k_point_codes' cell for points of the cube, the nearest boundary cell outside
-__device__ inline int clamped_cell21(float t, int off) {
-    const float ft = fminf(fmaxf(floorf(t), -4.0e9f), 4.0e9f);
-    const i64 c = (i64)ft + off, lim = (1 << ASR_MAX_LEVEL) - 1;
-    return (int)(c < 0 ? 0 : c > lim ? lim : c);
-}
-__device__ inline bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 __global__ void k_query_codes(asr_octree_frame f, const float* q, i64 m, u64* codes, int32_t* ids) {
     const i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     if (i >= m) return;
-    const float qx = q[3 * i], qy = q[3 * i + 1], qz = q[3 * i + 2];
-    const float inv = f.inv_voxel_size[ASR_MAX_LEVEL];
-    u64 code = (u64(1) << 63) - 1;  // non-finite rows last
-    if (finite3(qx, qy, qz))
-        code = asr_morton3d((u64)clamped_cell21(qx * inv, f.offset[0]), (u64)clamped_cell21(qy * inv, f.offset[1]),
-                            (u64)clamped_cell21(qz * inv, f.offset[2]));
-    codes[i] = code;
+    codes[i] = query_code21(f, q[3 * i], q[3 * i + 1], q[3 * i + 2]);
     ids[i] = (int32_t)i;
-}
-// distance from q to the nearer of the block's two faces on one axis, shrunk by the rounding margin; +inf for a face
-// on the root cube's boundary, negative when q lies outside the block.  c = centre cell of the block on `lev`.
-__device__ inline float nearest_face_gap(const asr_octree_frame& f, float q, int c, int lev, int off) {
-    const int s = ASR_MAX_LEVEL - lev;
-    const float vs = f.voxel_size[ASR_MAX_LEVEL];
-    const float keep = 0.99999904632568359375f, slack = 9.5367431640625e-7f;  // 1 - 2^-20, 2^-20
-    float g = __uint_as_float(0x7f800000u);
-    if (c - 1 > 0) {
-        const float face = (float)(((i64)(c - 1) << s) - off) * vs;
-        g = fminf(g, (q - face) * keep - fabsf(face) * slack);
-    }
-    if (c + 2 < (1 << lev)) {
-        const float face = (float)(((i64)(c + 2) << s) - off) * vs;
-        g = fminf(g, (face - q) * keep - fabsf(face) * slack);
-    }
-    return g;
 }
 __global__ __launch_bounds__(256) void k_nearest(asr_octree_frame f, const float4* __restrict__ sorted, CellIndex ci,
                                                  int lfine, int ldeep, const float* __restrict__ queries,
@@ -1919,66 +2033,7 @@ __global__ __launch_bounds__(256) void k_nearest(asr_octree_frame f, const float
         }
         return;
     }
-    const float inv = f.inv_voxel_size[ASR_MAX_LEVEL];
-    const int cx = clamped_cell21(qx * inv, f.offset[0]), cy = clamped_cell21(qy * inv, f.offset[1]),
-              cz = clamped_cell21(qz * inv, f.offset[2]);
-    // start level: as in k_knn, a query whose finest-level cell is crowded starts on the level at which its cell holds
-    // at most KNN_CROWD points (the codes are sorted down to ldeep)
-    int lev0 = lfine;
-    if (ldeep > lfine) {
-        const u64 code = asr_morton3d((u64)cx, (u64)cy, (u64)cz);
-        int b0, pop;
-        cell_range(ci, code >> (3 * (ASR_MAX_LEVEL - lfine)), lfine, b0, pop);
-        while (pop > KNN_CROWD && lev0 < ldeep) {
-            ++lev0;
-            cell_range(ci, code >> (3 * (ASR_MAX_LEVEL - lev0)), lev0, b0, pop);
-        }
-    }
-    u64 best = ~u64(0);  // (squared distance bits << 32) | original point index
-    for (int lev = lev0; lev >= 0; --lev) {
-        const int s = ASR_MAX_LEVEL - lev, lim = (1 << lev) - 1;
-        const int x = cx >> s, y = cy >> s, z = cz >> s;
-        int b = 0, cnt = 0;
-        if (lane < 27) {
-            const int xx = x + lane % 3 - 1, yy = y + (lane / 3) % 3 - 1, zz = z + lane / 9 - 1;
-            if (xx >= 0 && yy >= 0 && zz >= 0 && xx <= lim && yy <= lim && zz <= lim)
-                cell_range(ci, asr_morton3d((u64)xx, (u64)yy, (u64)zz), lev, b, cnt);
-        }
-        int pre = cnt;
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1) {
-            const int up = __shfl_up(pre, o, 64);
-            if (lane >= o) pre += up;
-        }
-        const int total = __shfl(pre, 26, 64);
-        if (total == 0) continue;  // (level 0 holds all n >= 1 points)
-        __builtin_amdgcn_wave_barrier();
-        if (lane < 27) {
-            s_pref[wave][lane + 1] = pre;
-            s_beg[wave][lane] = b;
-        }
-        if (lane == 0) s_pref[wave][0] = 0;
-        __builtin_amdgcn_wave_barrier();
-        for (int i0 = 0; i0 < total; i0 += 64) {
-            const int i = i0 + lane;
-            if (i < total) {
-                const float4 pt = radius_candidate(sorted, s_pref[wave], s_beg[wave], i);
-                const u64 key = ((u64)__float_as_uint(sqdist3(pt.x, pt.y, pt.z, qx, qy, qz)) << 32) |
-                                (u64)(u32)__float_as_int(pt.w);
-                best = key < best ? key : best;
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const u32 hi = __shfl_xor((u32)(best >> 32), o, 64), lo = __shfl_xor((u32)best, o, 64);
-            const u64 other = ((u64)hi << 32) | lo;
-            best = other < best ? other : best;
-        }
-        if (lev == 0) break;
-        const float g = fminf(fminf(nearest_face_gap(f, qx, x, lev, f.offset[0]), nearest_face_gap(f, qy, y, lev, f.offset[1])),
-                              nearest_face_gap(f, qz, z, lev, f.offset[2]));
-        if (g > 0.f && __uint_as_float((u32)(best >> 32)) < g * g) break;
-    }
+    const u64 best = nearest_walk<false>(f, sorted, ci, lfine, ldeep, qx, qy, qz, 0.f, lane, s_pref[wave], s_beg[wave]);
     if (lane == 0) {
         if (index_out) index_out[j] = (int32_t)(u32)best;
         if (sqdist_out) sqdist_out[j] = __uint_as_float((u32)(best >> 32));
@@ -1986,15 +2041,8 @@ __global__ __launch_bounds__(256) void k_nearest(asr_octree_frame f, const float
 }
 
 // ------------------------------------------------------------------------------------------
-// One ICP step (asr_hip_icp_step): the transformed source points are the queries of k_nearest's search, capped at a
-// distance, and the terms of the normal equations are accumulated behind it.
-// Cap: only points with d2 <= cap2 count.  The level walk is k_nearest's with one more exit: a level is also final when
-// cap2 < g * g (g: the shrunk gap to the nearest inner face of the block).  Every point outside the block has a COMPUTED
-// squared distance of at least g * g -- the statement the existing exit "best < g * g" rests on, with the same rounding
-// margin of nearest_face_gap: the margin bounds what sqdist3 can lose against the true gap, whatever the value it is then
-// compared with -- so all of them are beyond the cap and the best of the block, if it is within the cap, is the best of
-// the cloud within the cap.  Unlike in k_nearest the test also runs on a level whose block is empty: a source point with no
-// counterpart leaves at the first level whose cells are wider than the cap instead of climbing to the whole cloud.
+// One ICP step (asr_hip_icp_step): the transformed source points are the queries of nearest_walk, capped at a distance
+// (only points with d2 <= cap2 count), and the terms of the normal equations are accumulated behind it.
 // Sums: no float atomics.  The queries are taken in the Morton order of q; wave w owns the ICP_RUN consecutive queries
 // from w * ICP_RUN, lane t < 28 keeps entry t of (ata[21], atb[6], sq_residual) in a register across the run, lane 28
 // sq_distance, lane 29 the pair count.  The four waves of a block are added in wave order, k_icp_fold adds the blocks'
@@ -2022,80 +2070,8 @@ __global__ void k_icp_codes(asr_octree_frame f, IcpTransform x, const float* __r
     q[3 * i] = qx;
     q[3 * i + 1] = qy;
     q[3 * i + 2] = qz;
-    const float inv = f.inv_voxel_size[ASR_MAX_LEVEL];
-    u64 code = (u64(1) << 63) - 1;  // rows without a finite q last
-    if (finite3(qx, qy, qz))
-        code = asr_morton3d((u64)clamped_cell21(qx * inv, f.offset[0]), (u64)clamped_cell21(qy * inv, f.offset[1]),
-                            (u64)clamped_cell21(qz * inv, f.offset[2]));
-    codes[i] = code;
+    codes[i] = query_code21(f, qx, qy, qz);  // rows without a finite q last
     ids[i] = (int32_t)i;
-}
-// k_nearest's search of one finite query by one wave, capped: the smallest (squared distance bits << 32 | point index) of
-// the final level's block, the same value in every lane; ~0 when that block is empty
-__device__ inline u64 capped_nearest(const asr_octree_frame& f, const float4* __restrict__ sorted, const CellIndex& ci,
-                                     int lfine, int ldeep, float qx, float qy, float qz, float cap2, int lane, int* s_pref,
-                                     int* s_beg) {
-    const float inv = f.inv_voxel_size[ASR_MAX_LEVEL];
-    const int cx = clamped_cell21(qx * inv, f.offset[0]), cy = clamped_cell21(qy * inv, f.offset[1]),
-              cz = clamped_cell21(qz * inv, f.offset[2]);
-    int lev0 = lfine;
-    if (ldeep > lfine) {
-        const u64 code = asr_morton3d((u64)cx, (u64)cy, (u64)cz);
-        int b0, pop;
-        cell_range(ci, code >> (3 * (ASR_MAX_LEVEL - lfine)), lfine, b0, pop);
-        while (pop > KNN_CROWD && lev0 < ldeep) {
-            ++lev0;
-            cell_range(ci, code >> (3 * (ASR_MAX_LEVEL - lev0)), lev0, b0, pop);
-        }
-    }
-    u64 best = ~u64(0);
-    for (int lev = lev0; lev >= 0; --lev) {
-        const int s = ASR_MAX_LEVEL - lev, lim = (1 << lev) - 1;
-        const int x = cx >> s, y = cy >> s, z = cz >> s;
-        int b = 0, cnt = 0;
-        if (lane < 27) {
-            const int xx = x + lane % 3 - 1, yy = y + (lane / 3) % 3 - 1, zz = z + lane / 9 - 1;
-            if (xx >= 0 && yy >= 0 && zz >= 0 && xx <= lim && yy <= lim && zz <= lim)
-                cell_range(ci, asr_morton3d((u64)xx, (u64)yy, (u64)zz), lev, b, cnt);
-        }
-        int pre = cnt;
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1) {
-            const int up = __shfl_up(pre, o, 64);
-            if (lane >= o) pre += up;
-        }
-        const int total = __shfl(pre, 26, 64);
-        if (total > 0) {
-            __builtin_amdgcn_wave_barrier();
-            if (lane < 27) {
-                s_pref[lane + 1] = pre;
-                s_beg[lane] = b;
-            }
-            if (lane == 0) s_pref[0] = 0;
-            __builtin_amdgcn_wave_barrier();
-            for (int i0 = 0; i0 < total; i0 += 64) {
-                const int i = i0 + lane;
-                if (i < total) {
-                    const float4 pt = radius_candidate(sorted, s_pref, s_beg, i);
-                    const u64 key = ((u64)__float_as_uint(sqdist3(pt.x, pt.y, pt.z, qx, qy, qz)) << 32) |
-                                    (u64)(u32)__float_as_int(pt.w);
-                    best = key < best ? key : best;
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const u32 hi = __shfl_xor((u32)(best >> 32), o, 64), lo = __shfl_xor((u32)best, o, 64);
-                const u64 other = ((u64)hi << 32) | lo;
-                best = other < best ? other : best;
-            }
-        }
-        if (lev == 0) break;
-        const float g = fminf(fminf(nearest_face_gap(f, qx, x, lev, f.offset[0]), nearest_face_gap(f, qy, y, lev, f.offset[1])),
-                              nearest_face_gap(f, qz, z, lev, f.offset[2]));
-        // (an empty block has best = ~0, whose distance bits are a NaN: the first comparison is false)
-        if (g > 0.f && (__uint_as_float((u32)(best >> 32)) < g * g || cap2 < g * g)) break;
-    }
-    return best;
 }
 // the row (a, r) of one pair and one direction n: (e0..e5) = (u x n, n), e6 = r; d = u - v.  Named members and a chain of
 // selects: an array indexed by the lane's entry would be placed in LDS.
@@ -2152,7 +2128,7 @@ __global__ __launch_bounds__(256) void k_icp_pairs(asr_octree_frame f, const flo
         int32_t hit = -1;
         float yx = 0.f, yy = 0.f, yz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
         if (finite3(qx, qy, qz)) {
-            const u64 best = capped_nearest(f, sorted, ci, lfine, ldeep, qx, qy, qz, cap2, lane, s_pref[wave], s_beg[wave]);
+            const u64 best = nearest_walk<true>(f, sorted, ci, lfine, ldeep, qx, qy, qz, cap2, lane, s_pref[wave], s_beg[wave]);
             if (best != ~u64(0) && __uint_as_float((u32)(best >> 32)) <= cap2) {
                 hit = (int32_t)(u32)best;
                 yx = target[3 * (i64)hit];
@@ -2229,26 +2205,16 @@ __global__ __launch_bounds__(32 * ICP_FOLD) void k_icp_fold(const double* __rest
 }
 
 // ------------------------------------------------------------------------------------------
-// Exact k-nearest-neighbour LISTS (asr_hip_knn_index): one wave per point in Morton order, the level walk of k_knn /
-// k_nearest.  The best 64 (squared distance bits << 32 | point index) keys seen on a level are one key per lane, ascending
-// over the lanes; row i of the output is the first k of them.  Candidates come 64 at a time: a batch in which no key lies
-// below the current k-th one (a ballot) is skipped, one with at most KNN_INSERT such keys has them inserted one by one,
-// any other is sorted by a bitonic network of lane shuffles, reversed and merged: min(best[l], batch[63 - l]) is a
-// bitonic sequence that holds the 64 smallest of the 128, six more compare-exchange steps sort it.  Keys are distinct (the index is part of them), so the order (d2, index) is total.
-// Acceptance of a level is k_nearest's with the k-th key in place of the best: every point outside the 3^3 block has a
-// COMPUTED squared distance of at least g^2 (g: the shrunk distance to the nearest inner face of the block), and the test
-// d2_k < g^2 is strict, so such a point cannot even tie with the k-th key -- no smaller index is lost at the block's
-// boundary.  A level that is not accepted hands its k-th key down as a bound (its block is a subset of the next one's),
-// and the list starts again, because the next block holds the same points once more.
+// Exact k-nearest-neighbour LISTS (asr_hip_knn_index): one wave per point in Morton order, the level walk with the k-th
+// key in place of the best.  The best 64 (squared distance bits << 32 | point index) keys seen on a level are one key per
+// lane, ascending over the lanes; row i of the output is the first k of them.  Candidates come 64 at a time: a batch in
+// which no key lies below the current k-th one (a ballot) is skipped, one with at most KNN_INSERT such keys has them
+// inserted one by one, any other is sorted by a bitonic network of lane shuffles, reversed and merged: min(best[l],
+// batch[63 - l]) is a bitonic sequence that holds the 64 smallest of the 128, six more compare-exchange steps sort it.
+// Keys are distinct (the index is part of them), so the order (d2, index) is total.  A level that is not accepted hands
+// its k-th key down as a bound (its block is a subset of the next one's), and the list starts again, because the next
+// block holds the same points once more.
 // ------------------------------------------------------------------------------------------
-__device__ inline u64 shfl_xor_u64(u64 v, int o) {
-    const u32 hi = __shfl_xor((u32)(v >> 32), o, 64), lo = __shfl_xor((u32)v, o, 64);
-    return ((u64)hi << 32) | lo;
-}
-__device__ inline u64 shfl_u64(u64 v, int src) {
-    const u32 hi = __shfl((u32)(v >> 32), src, 64), lo = __shfl((u32)v, src, 64);
-    return ((u64)hi << 32) | lo;
-}
 constexpr int KNN_INSERT = 12;  // survivors of a batch up to which they are inserted one by one instead of sorted and merged
 __global__ __launch_bounds__(256) void k_knn_index(asr_octree_frame f, const float4* __restrict__ sorted, i64 n, CellIndex ci,
                                                    int lfine, int ldeep, int k, int32_t* __restrict__ index_out,
@@ -2274,14 +2240,10 @@ __global__ __launch_bounds__(256) void k_knn_index(asr_octree_frame f, const flo
     u64 best = ~u64(0);   // lane l: the l-th smallest key of this level so far
     u64 bound = ~u64(0);  // the k-th key of a finer level: no key of the answer is larger
     for (int lev = lev0; lev >= 0; --lev) {
-        const int sh = ASR_MAX_LEVEL - lev, lim = (1 << lev) - 1;
+        const int sh = ASR_MAX_LEVEL - lev;
         const int x = cx >> sh, y = cy >> sh, z = cz >> sh;
-        int b = 0, cnt = 0;
-        if (lane < 27) {
-            const int xx = x + lane % 3 - 1, yy = y + (lane / 3) % 3 - 1, zz = z + lane / 9 - 1;
-            if (xx >= 0 && yy >= 0 && zz >= 0 && xx <= lim && yy <= lim && zz <= lim)
-                cell_range(ci, asr_morton3d((u64)xx, (u64)yy, (u64)zz), lev, b, cnt);
-        }
+        int b, cnt;
+        block27_ranges(ci, x, y, z, lev, lane, b, cnt);
         int pre = cnt;
 #pragma unroll
         for (int o = 1; o < 32; o <<= 1) {
@@ -3773,6 +3735,35 @@ static int deepen_crowded_index(asr_hip_context* ctx, const float* pts, RadiusSt
     }
     return ASR_HIP_OK;
 }
+// The index of the nearest-neighbour searches: levels 0..lfine hashed, the points of a crowded cloud sorted down to ldeep.
+// Host round trips: the cell counts of the build and the largest cell population.
+struct KnnIndex {
+    RadiusState st;
+    int lfine = 0, ldeep = 0;
+};
+static int build_knn_index(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, int lfine,
+                           const char* what, KnnIndex& ix) {
+    ix.lfine = lfine;
+    ASR_TRY(build_point_index_grown(ctx, frame, pts, n, 0, lfine, ix.st, what));
+    ix.st.lhash = lfine;
+    return deepen_crowded_index(ctx, pts, ix.st, lfine, &ix.ldeep);
+}
+// The queries' Morton order: alloc(), a kernel that fills codes_u / ids_u (k_query_codes, k_icp_codes), then sort() on the
+// bits the index is hashed on; `ids` is the order.  Two steps so that a caller's own arrays keep their place in the arena.
+struct QueryOrder {
+    u64 *codes_u = nullptr, *codes = nullptr;
+    int32_t *ids_u = nullptr, *ids = nullptr;
+    bool alloc(asr_hip_context* ctx, i64 m) {
+        codes_u = arena_alloc<u64>(ctx->scratch, m);
+        codes = arena_alloc<u64>(ctx->scratch, m);
+        ids_u = arena_alloc<int32_t>(ctx->scratch, m);
+        ids = arena_alloc<int32_t>(ctx->scratch, m);
+        return codes_u && codes && ids_u && ids;
+    }
+    int sort(asr_hip_context* ctx, i64 m, int lfine) {
+        return sort_pairs<u64, int32_t>(ctx, ctx->scratch, codes_u, codes, ids_u, ids, m, 63, 3 * (ASR_MAX_LEVEL - lfine));
+    }
+};
 
 // KDTree::ComputeKRadius / ComputeInlier (cpp/lib/nsearch.cpp:30-86)
 int asr_geom_knn(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, int k,
@@ -3782,13 +3773,11 @@ int asr_geom_knn(asr_hip_context* ctx, const asr_octree_frame* frame, const floa
     if (n <= 0) return ASR_HIP_OK;
     if (k < 1) ASR_FAIL(ctx, ASR_HIP_EINVAL, "knn: k must be >= 1");
     if (n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "too many points for int32 indices");
-    const int lfine = knn_fine_level(n);
-    RadiusState st;
+    KnnIndex ix;
     HostFlags host;
-    ASR_TRY(build_point_index_grown(ctx, frame, pts, n, 0, lfine, st, "cell table overflow"));
-    st.lhash = lfine;
-    int ldeep;
-    ASR_TRY(deepen_crowded_index(ctx, pts, st, lfine, &ldeep));
+    ASR_TRY(build_knn_index(ctx, frame, pts, n, knn_fine_level(n), "cell table overflow", ix));
+    const RadiusState& st = ix.st;
+    const int lfine = ix.lfine, ldeep = ix.ldeep;
     const bool fast = !inlier_out && radii_out && k <= 32 && n >= k && ctx->opt.knn_cells;
     if (fast) {
         // cell-parallel pass, then the wave-per-point kernel for what it could not certify
@@ -3831,51 +3820,32 @@ int asr_geom_knn(asr_hip_context* ctx, const asr_octree_frame* frame, const floa
     return ASR_HIP_OK;
 }
 
-// asr_hip_nearest_point: the kNN search's point index (levels 0..lfine hashed, crowded clouds sorted eight levels
-// deeper), the queries' Morton order, one k_nearest launch.  Host round trips: the cell counts of the index build, the
-// largest cell population; the search itself is enqueued and not waited for.
+// asr_hip_nearest_point: the index, the queries' Morton order, one k_nearest launch.  The search itself is enqueued and not
+// waited for.
 int asr_geom_nearest(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, const float* queries,
                      i64 m, int32_t* index_out, float* sqdist_out) {
     ASR_TRY(ensure_flags(ctx));
     if (m <= 0 || (!index_out && !sqdist_out)) return ASR_HIP_OK;
-    const int lfine = knn_fine_level(n);
-    RadiusState st;
-    ASR_TRY(build_point_index_grown(ctx, frame, pts, n, 0, lfine, st, "nearest point: cell table overflow"));
-    st.lhash = lfine;
-    int ldeep;
-    ASR_TRY(deepen_crowded_index(ctx, pts, st, lfine, &ldeep));
-    u64* qcodes_u = arena_alloc<u64>(ctx->scratch, m);
-    u64* qcodes = arena_alloc<u64>(ctx->scratch, m);
-    int32_t* qids_u = arena_alloc<int32_t>(ctx->scratch, m);
-    int32_t* qids = arena_alloc<int32_t>(ctx->scratch, m);
-    if (!qcodes_u || !qcodes || !qids_u || !qids) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-    k_query_codes<<<grid_for(m, BLK), BLK, 0, ctx->stream>>>(*frame, queries, m, qcodes_u, qids_u);
+    KnnIndex ix;
+    ASR_TRY(build_knn_index(ctx, frame, pts, n, knn_fine_level(n), "nearest point: cell table overflow", ix));
+    QueryOrder qo;
+    if (!qo.alloc(ctx, m)) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    k_query_codes<<<grid_for(m, BLK), BLK, 0, ctx->stream>>>(*frame, queries, m, qo.codes_u, qo.ids_u);
     ASR_CHECK_LAUNCH(ctx);
-    ASR_TRY((sort_pairs<u64, int32_t>(ctx, ctx->scratch, qcodes_u, qcodes, qids_u, qids, m, 63,
-                                      3 * (ASR_MAX_LEVEL - lfine))));
-    k_nearest<<<grid_for(m, 4), BLK, 0, ctx->stream>>>(*frame, st.sorted, st.index(), lfine, ldeep, queries, qids, m,
-                                                       index_out, sqdist_out);
+    ASR_TRY(qo.sort(ctx, m, ix.lfine));
+    k_nearest<<<grid_for(m, 4), BLK, 0, ctx->stream>>>(*frame, ix.st.sorted, ix.st.index(), ix.lfine, ix.ldeep, queries,
+                                                       qo.ids, m, index_out, sqdist_out);
     ASR_CHECK_LAUNCH(ctx);
     return ASR_HIP_OK;
 }
 
 // asr_hip_icp_step / asr_hip_register_points: asr_geom_nearest's index of the target, built once per call; per step the
 // transformed queries and their Morton order, one k_icp_pairs launch, k_icp_fold and the read-back of the sums.
-struct IcpIndex {
-    RadiusState st;
-    int lfine = 0, ldeep = 0;
-};
-static int icp_build_index(asr_hip_context* ctx, const asr_octree_frame* frame, const float* target, i64 n, IcpIndex& ix) {
-    ix.lfine = knn_fine_level(n);
-    ASR_TRY(build_point_index_grown(ctx, frame, target, n, 0, ix.lfine, ix.st, "icp: cell table overflow"));
-    ix.st.lhash = ix.lfine;
-    return deepen_crowded_index(ctx, target, ix.st, ix.lfine, &ix.ldeep);
-}
 static_assert(offsetof(asr_icp_sums, atb) == 21 * 8 && offsetof(asr_icp_sums, sq_residual) == 27 * 8 &&
                       offsetof(asr_icp_sums, sq_distance) == 28 * 8 && offsetof(asr_icp_sums, pairs) == 29 * 8,
               "k_icp_fold writes the sums in the struct's order");
 // one step on a built index; its temporaries are taken from the scratch arena and given back
-static int icp_step_indexed(asr_hip_context* ctx, const asr_octree_frame* frame, const IcpIndex& ix, const float* target,
+static int icp_step_indexed(asr_hip_context* ctx, const asr_octree_frame* frame, const KnnIndex& ix, const float* target,
                             const float* normals, const float* source, i64 m, const double transform[12],
                             const double origin[3], float max_distance, asr_icp_sums* sums, int32_t* index_out) {
     memset(sums, 0, sizeof(*sums));
@@ -3885,29 +3855,25 @@ static int icp_step_indexed(asr_hip_context* ctx, const asr_octree_frame* frame,
     arena_mark(ctx->scratch, mark);
     const i64 nb = (m + 4 * ICP_RUN - 1) / (4 * ICP_RUN);
     float* q = arena_alloc<float>(ctx->scratch, 3 * m);
-    u64* qcodes_u = arena_alloc<u64>(ctx->scratch, m);
-    u64* qcodes = arena_alloc<u64>(ctx->scratch, m);
-    int32_t* qids_u = arena_alloc<int32_t>(ctx->scratch, m);
-    int32_t* qids = arena_alloc<int32_t>(ctx->scratch, m);
+    QueryOrder qo;
+    const bool qo_ok = qo.alloc(ctx, m);
     double* partial = arena_alloc<double>(ctx->scratch, nb * ICP_STRIDE);
     double* dsums = arena_alloc<double>(ctx->scratch, ICP_STRIDE);
-    if (!q || !qcodes_u || !qcodes || !qids_u || !qids || !partial || !dsums)
-        ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    if (!q || !qo_ok || !partial || !dsums) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
     IcpTransform x;
     memcpy(x.t, transform, sizeof(x.t));
     memcpy(x.o, origin, sizeof(x.o));
-    k_icp_codes<<<grid_for(m, BLK), BLK, 0, ctx->stream>>>(*frame, x, source, m, q, qcodes_u, qids_u);
+    k_icp_codes<<<grid_for(m, BLK), BLK, 0, ctx->stream>>>(*frame, x, source, m, q, qo.codes_u, qo.ids_u);
     ASR_CHECK_LAUNCH(ctx);
-    ASR_TRY((sort_pairs<u64, int32_t>(ctx, ctx->scratch, qcodes_u, qcodes, qids_u, qids, m, 63,
-                                      3 * (ASR_MAX_LEVEL - ix.lfine))));
+    ASR_TRY(qo.sort(ctx, m, ix.lfine));
     const float cap2 = max_distance * max_distance;
     if (normals)
         k_icp_pairs<true><<<(unsigned)nb, BLK, 0, ctx->stream>>>(*frame, ix.st.sorted, ix.st.index(), ix.lfine, ix.ldeep, q,
-                                                                 qids, m, target, normals, x.o[0], x.o[1], x.o[2], cap2,
+                                                                 qo.ids, m, target, normals, x.o[0], x.o[1], x.o[2], cap2,
                                                                  index_out, partial);
     else
         k_icp_pairs<false><<<(unsigned)nb, BLK, 0, ctx->stream>>>(*frame, ix.st.sorted, ix.st.index(), ix.lfine, ix.ldeep, q,
-                                                                  qids, m, target, nullptr, x.o[0], x.o[1], x.o[2], cap2,
+                                                                  qo.ids, m, target, nullptr, x.o[0], x.o[1], x.o[2], cap2,
                                                                   index_out, partial);
     ASR_CHECK_LAUNCH(ctx);
     k_icp_fold<<<1, 32 * ICP_FOLD, 0, ctx->stream>>>(partial, nb, dsums);
@@ -3921,16 +3887,16 @@ int asr_geom_icp_step(asr_hip_context* ctx, const asr_octree_frame* frame, const
                       const float* source, i64 m, const double transform[12], const double origin[3], float max_distance,
                       asr_icp_sums* sums, int32_t* index_out) {
     ASR_TRY(ensure_flags(ctx));
-    IcpIndex ix;
-    if (m > 0) ASR_TRY(icp_build_index(ctx, frame, target, n, ix));
+    KnnIndex ix;
+    if (m > 0) ASR_TRY(build_knn_index(ctx, frame, target, n, knn_fine_level(n), "icp: cell table overflow", ix));
     return icp_step_indexed(ctx, frame, ix, target, normals, source, m, transform, origin, max_distance, sums, index_out);
 }
 int asr_geom_register(asr_hip_context* ctx, const asr_octree_frame* frame, const float* target, i64 n, const float* normals,
                       const float* source, i64 m, const asr_icp_params* params, double transform[12],
                       asr_icp_report* report) {
     ASR_TRY(ensure_flags(ctx));
-    IcpIndex ix;
-    if (m > 0) ASR_TRY(icp_build_index(ctx, frame, target, n, ix));
+    KnnIndex ix;
+    if (m > 0) ASR_TRY(build_knn_index(ctx, frame, target, n, knn_fine_level(n), "icp: cell table overflow", ix));
     double origin[3];
     for (int a = 0; a < 3; ++a)
         origin[a] = (double)((1 << (ASR_MAX_LEVEL - 1)) - frame->offset[a]) * (double)frame->voxel_size[ASR_MAX_LEVEL];
@@ -3958,8 +3924,8 @@ int asr_geom_register(asr_hip_context* ctx, const asr_octree_frame* frame, const
     return ASR_HIP_OK;
 }
 
-// asr_hip_knn_index: the index of asr_geom_knn / asr_geom_nearest and one k_knn_index launch.  Host round trips: the cell
-// counts of the index build and the largest cell population; the search itself is enqueued and not waited for.
+// asr_hip_knn_index: the index, one level finer, and one k_knn_index launch.  The search itself is enqueued and not waited
+// for.
 int asr_geom_knn_index(asr_hip_context* ctx, const asr_octree_frame* frame, const float* pts, i64 n, int k,
                        int32_t* index_out, float* sqdist_out) {
     ASR_TRY(ensure_flags(ctx));
@@ -3967,15 +3933,12 @@ int asr_geom_knn_index(asr_hip_context* ctx, const asr_octree_frame* frame, cons
     // cube, a scanned SURFACE has dozens of points in its occupied cells there and a wave would walk a few hundred
     // candidates per point; one level down it is a quarter.  Where that block holds fewer than k points (a cloud that does
     // fill the cube) the walk moves up after the 27 look-ups.
-    const int lfine = std::min(ASR_MAX_LEVEL, knn_fine_level(n) + 1);
-    RadiusState st;
-    ASR_TRY(build_point_index_grown(ctx, frame, pts, n, 0, lfine, st, "knn index: cell table overflow"));
-    st.lhash = lfine;
-    int ldeep;
-    ASR_TRY(deepen_crowded_index(ctx, pts, st, lfine, &ldeep));
+    KnnIndex ix;
+    ASR_TRY(build_knn_index(ctx, frame, pts, n, std::min(ASR_MAX_LEVEL, knn_fine_level(n) + 1),
+                            "knn index: cell table overflow", ix));
     if (!index_out && !sqdist_out) return ASR_HIP_OK;  // (the points have been checked)
-    k_knn_index<<<grid_for(n, 4), BLK, 0, ctx->stream>>>(*frame, st.sorted, n, st.index(), lfine, ldeep, k, index_out,
-                                                         sqdist_out);
+    k_knn_index<<<grid_for(n, 4), BLK, 0, ctx->stream>>>(*frame, ix.st.sorted, n, ix.st.index(), ix.lfine, ix.ldeep, k,
+                                                         index_out, sqdist_out);
     ASR_CHECK_LAUNCH(ctx);
     return ASR_HIP_OK;
 }

@@ -406,6 +406,55 @@ def test_knn_radius_cell_path_equals_the_wave_path():
     assert np.array_equal(got, flat)
 
 
+def coincident_cloud():
+    """600 copies of one point among 100 uniform points of the unit cube (indices shuffled), radii for the inlier vote, and
+    the brute-force references.  The copies' radii: of the 24 copies with the smallest indices two have 0.5, the others 1.0;
+    the later copies alternate between 0.5 and 2.0.  A copy with radius 1.0 is voted for by the copies below 0.9, i.e. by
+    exactly two of its 24 nearest neighbours (the 24 smallest indices among 600 ties at distance 0) -- and by half of any
+    other choice of 24."""
+    rng = np.random.default_rng(41)
+    pts = rng.uniform(0, 1, size=(700, 3)).astype(np.float32)
+    copies = np.sort(rng.permutation(700)[:600])
+    pts[copies] = np.float32([0.3, 0.6, 0.45])
+    rad = np.ones(700, np.float32)
+    rad[copies[[3, 17]]] = 0.5
+    rad[copies[24::2]] = 0.5
+    rad[copies[25::2]] = 2.0
+    d2 = ((pts[:, None, :] - pts[None, :, :]) ** 2)
+    d2 = (d2[..., 0] + d2[..., 1]) + d2[..., 2]
+    order = np.argsort(d2, axis=1, kind="stable")[:, :24]  # stable: equal distances keep index order
+    votes = (rad[order] < (rad * np.float32(0.9))[:, None]).sum(1)
+    return pts, rad, copies, O.knn_radius(pts, 24), votes
+
+
+@pytest.mark.gpu
+def test_knn_radius_and_inlier_vote_with_600_coincident_points():
+    """k_knn's pool overflow: 600 candidates at distance 0 fill the 8 slots of all 64 lanes (512) and the next batch
+    overflows, so the k-th distance comes from the bit search streamed over the candidates, and the vote picks the 24
+    smallest indices among the 600 ties with the index bit search.  600 < KNN_CROWD: no deeper start level.  The radii of
+    the cell path, of the wave path and of the brute force are equal, and the vote equals the brute force with ties in
+    ascending index (test_inlier_vote_on_a_crowded_lattice's rule)."""
+    import adaptivesurfacereconstruction as asr
+    from asr_hip import ops
+    pts, rad, copies, want_r, votes = coincident_cloud()
+    assert np.all(want_r[copies] == 0) and np.all(want_r[np.setdiff1d(np.arange(700), copies)] > 0)
+    one = copies[rad[copies] == 1.0]
+    assert len(one) == 22 and np.all(votes[one] == 2) and np.all(votes[copies[25::2]] == 24)
+    ctx = ops.context(torch.device("cuda:0"))
+    tree = asr.KDTree(pts)
+    try:
+        ctx.set_option("knn_cells", 1)
+        fast = tree.compute_k_radius(24)
+        ctx.set_option("knn_cells", 0)
+        slow = tree.compute_k_radius(24)
+        inl = tree.compute_inlier(rad, radius_fraction=0.9, k=24, outlier_threshold=3)
+    finally:
+        ctx.set_option("knn_cells", 1)
+    assert np.array_equal(fast, slow)
+    assert slow.dtype == np.float32 and np.array_equal(slow, want_r)
+    assert np.array_equal(inl, votes < 3)
+
+
 @pytest.mark.parametrize("shift", [0.0, 100.0], ids=["frame-at-origin", "frame-100-units-away"])
 def test_aligned_search_finds_the_pairs_of_the_rounding_margin(gpu, shift):
     """The aggregation search of the whole path covers the ball of voxel (x, y, z, L) with the 4^3 cells of level
