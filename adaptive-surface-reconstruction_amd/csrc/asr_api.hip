@@ -1030,14 +1030,29 @@ struct Net {
     // features -- except this one, the aggregation's per-pair array, which every rank holds in full (quirk B.2)
     const float* replicated_imp = nullptr;
 
-    // rows / plan of a convolution over the list `rs` and the halo exchange of its input (no-op on one GPU)
-    int shard_hook(const i64* rs, Feat in, const float* imp, const int32_t** perm, i64* num_out,
-                   const asr_conv_plan** plan) {
-        *plan = nullptr;
-        if (!ctx->shard) return ASR_HIP_OK;
-        float* imp_x = (imp && imp != replicated_imp) ? const_cast<float*>(imp) : nullptr;
-        return asr_shard_before_conv(ctx, ctx->shard, rs, in.p, in.ld * (i64)esz(), in.c * (i64)esz(), imp_x, in.amax, perm,
-                                     num_out, plan);
+    // The rows a convolution over `l` computes, with their plan: the list's own or, in a sharded forward, the ones this rank
+    // owns once the halo of its input has been exchanged.  Fills what every argument block has in common.
+    int begin_conv(const NbList& l, Feat in, const float* imp, asr_sparse_conv_args& a, const asr_conv_plan** rows) {
+        *rows = &l;
+        if (ctx->shard) {
+            float* imp_x = (imp && imp != replicated_imp) ? const_cast<float*>(imp) : nullptr;
+            ASR_TRY(asr_shard_before_conv(ctx, ctx->shard, l, in.p, in.ld * (i64)esz(), in.c * (i64)esz(), imp_x, in.amax, rows));
+        }
+        memset(&a, 0, sizeof(a));
+        a.inp_features = in.p;
+        a.inp_ld = in.ld;
+        a.inp_importance = imp;
+        a.neighbors_index = l.nidx;
+        a.neighbors_kernel_index = l.kidx;
+        a.neighbors_row_splits = l.rs;
+        a.num_out = (*rows)->num_out;
+        a.num_inp = l.num_inp;
+        a.kernel_size = l.K;
+        a.cin = in.c;
+        a.relu = 1;
+        a.row_perm = (*rows)->perm;
+        a.inp_absmax = in.amax;
+        return ASR_HIP_OK;
     }
 
     // f16x2: a zeroed device scalar for the running maximum of one activation buffer (nullptr in the other modes)
@@ -1082,16 +1097,10 @@ struct Net {
     }
     // dispatch of one assembled argument block: f32 kernel or a 16-bit variant; out_f32: the layer's output
     // feeds the decoder (f32 `code`)
-    int launch(asr_sparse_conv_args& a, const asr_weight* ka, const asr_weight* kb, bool out_f32,
-               const asr_conv_plan* shard_plan = nullptr) {
+    int launch(asr_sparse_conv_args& a, const asr_weight* ka, const asr_weight* kb, bool out_f32, const asr_conv_plan* plan) {
         if (precision == 0) return asr_conv_sparse(ctx, &a);
         const void* pk = nullptr;
         ASR_TRY(packed(ka, kb, &pk));
-        const asr_conv_plan* plan = shard_plan;
-        if (!ctx->shard) {
-            auto pl = ctx->conv_plans.find(a.neighbors_row_splits);
-            plan = pl == ctx->conv_plans.end() ? nullptr : &pl->second;
-        }
         return asr_conv_sparse16(ctx, &a, pk, precision, precision == ASR_CONV16_F16 && !out_f32, plan);
     }
 
@@ -1106,98 +1115,66 @@ struct Net {
     }
 
     // one SpecialSparseConv (+bias, ReLU): models/common_torch.py:95-148
-    int conv(const std::string& prefix, int K, Feat in, const int32_t* nidx, const uint8_t* nk,
-             const i64* rs, const int32_t* perm, i64 num_out, i64 num_inp, const float* imp,
-             int normalize, float* out, i64 out_ld, int expect_cout, float* out_imp,
-             const float* residual, i64 residual_ld, bool out_f32 = false, unsigned* out_amax = nullptr) {
+    int conv(const std::string& prefix, Feat in, const NbList& l, const float* imp, int normalize, float* out, i64 out_ld,
+             int expect_cout, float* out_imp, const float* residual, i64 residual_ld, bool out_f32 = false,
+             unsigned* out_amax = nullptr) {
         const asr_weight *k, *b;
         ASR_TRY(get(prefix + ".kernel", 3, &k));
         ASR_TRY(get(prefix + ".bias", 1, &b));
-        if (k->shape[0] != K || k->shape[1] != in.c || (expect_cout > 0 && k->shape[2] != expect_cout) ||
+        if (k->shape[0] != l.K || k->shape[1] != in.c || (expect_cout > 0 && k->shape[2] != expect_cout) ||
             b->shape[0] != k->shape[2])
             ASR_FAIL(ctx, ASR_HIP_EWEIGHT, "weight '%s.kernel' has shape [%lld,%lld,%lld], expected [%d,%d,%d]",
                      prefix.c_str(), (long long)k->shape[0], (long long)k->shape[1],
-                     (long long)k->shape[2], K, in.c, expect_cout);
-        const asr_conv_plan* shard_plan = nullptr;
-        ASR_TRY(shard_hook(rs, in, imp, &perm, &num_out, &shard_plan));
+                     (long long)k->shape[2], l.K, in.c, expect_cout);
         asr_sparse_conv_args a;
-        memset(&a, 0, sizeof(a));
+        const asr_conv_plan* rows;
+        ASR_TRY(begin_conv(l, in, imp, a, &rows));
         a.filters = k->data;
-        a.inp_features = in.p;
-        a.inp_ld = in.ld;
-        a.inp_importance = imp;
-        a.neighbors_index = nidx;
-        a.neighbors_kernel_index = nk;
-        a.neighbors_row_splits = rs;
-        a.num_out = num_out;
-        a.num_inp = num_inp;
-        a.kernel_size = K;
-        a.cin = in.c;
         a.cout = (int)k->shape[2];
         a.normalize = normalize;
         a.bias = b->data;
-        a.relu = 1;
         a.residual = residual;
         a.residual_ld = residual_ld;
         a.out = out;
         a.out_ld = out_ld;
         a.out_importance = out_imp;
-        a.row_perm = perm;
-        a.inp_absmax = in.amax;
         a.out_absmax = out_amax;
-        return launch(a, k, nullptr, out_f32, shard_plan);
+        return launch(a, k, nullptr, out_f32, rows);
     }
     // conv1a + conv1b of a block in one launch (second filter bank of asr_sparse_conv_args): same
     // gather, one extra column tile.  Falls back to two launches for widths the fused kernel does not take.
-    int conv_ab(const std::string& name, int K, Feat in, const int32_t* nidx, const uint8_t* nk, const i64* rs,
-                const int32_t* perm, i64 num_out, i64 num_inp, const float* imp, float* out, i64 out_ld, int ca,
-                int cb, float* out_imp, unsigned* out_amax) {
+    int conv_ab(const std::string& name, Feat in, const NbList& l, const float* imp, float* out, i64 out_ld, int ca, int cb,
+                float* out_imp, unsigned* out_amax) {
         const asr_weight *ka, *ba, *kb, *bb;
         ASR_TRY(get(name + ".conv1a.kernel", 3, &ka));
         ASR_TRY(get(name + ".conv1a.bias", 1, &ba));
         ASR_TRY(get(name + ".conv1b.kernel", 3, &kb));
         ASR_TRY(get(name + ".conv1b.bias", 1, &bb));
-        const bool fused = ca % 16 == 8 && cb == 8 && in.c % 8 == 0 && in.ld % 8 == 0 && ka->shape[0] == K &&
-                           kb->shape[0] == K && ka->shape[1] == in.c && kb->shape[1] == in.c &&
+        const bool fused = ca % 16 == 8 && cb == 8 && in.c % 8 == 0 && in.ld % 8 == 0 && ka->shape[0] == l.K &&
+                           kb->shape[0] == l.K && ka->shape[1] == in.c && kb->shape[1] == in.c &&
                            ka->shape[2] == ca && kb->shape[2] == cb && ba->shape[0] == ca && bb->shape[0] == cb &&
                            (uintptr_t)kb->data % 16 == 0 && (uintptr_t)ka->data % 16 == 0 &&
                            (uintptr_t)in.p % 16 == 0;
         if (!fused) {
-            ASR_TRY(conv(name + ".conv1a", K, in, nidx, nk, rs, perm, num_out, num_inp, nullptr, 0, out, out_ld, ca,
-                         nullptr, nullptr, 0, false, out_amax));
-            return conv(name + ".conv1b", K, in, nidx, nk, rs, perm, num_out, num_inp, imp, 1, col(out, ca), out_ld,
-                        cb, out_imp, nullptr, 0, false, out_amax);
+            ASR_TRY(conv(name + ".conv1a", in, l, nullptr, 0, out, out_ld, ca, nullptr, nullptr, 0, false, out_amax));
+            return conv(name + ".conv1b", in, l, imp, 1, col(out, ca), out_ld, cb, out_imp, nullptr, 0, false, out_amax);
         }
-        const asr_conv_plan* shard_plan = nullptr;
-        ASR_TRY(shard_hook(rs, in, imp, &perm, &num_out, &shard_plan));
         asr_sparse_conv_args a;
-        memset(&a, 0, sizeof(a));
+        const asr_conv_plan* rows;
+        ASR_TRY(begin_conv(l, in, imp, a, &rows));
         a.filters = ka->data;
         a.filters_b = kb->data;
-        a.inp_features = in.p;
-        a.inp_ld = in.ld;
-        a.inp_importance = imp;
-        a.neighbors_index = nidx;
-        a.neighbors_kernel_index = nk;
-        a.neighbors_row_splits = rs;
-        a.num_out = num_out;
-        a.num_inp = num_inp;
-        a.kernel_size = K;
-        a.cin = in.c;
         a.cout = ca;
         a.cout_b = cb;
         a.normalize = 1;
         a.bias = ba->data;
         a.bias_b = bb->data;
-        a.relu = 1;
         a.out = out;
         a.out_ld = out_ld;
         a.out_importance = out_imp;
-        a.row_perm = perm;
         a.algo = 2;
-        a.inp_absmax = in.amax;
         a.out_absmax = out_amax;
-        return launch(a, ka, kb, false, shard_plan);
+        return launch(a, ka, kb, false, rows);
     }
     int cout_of(const std::string& prefix, int* c) {
         const asr_weight* k;
@@ -1208,12 +1185,12 @@ struct Net {
 
     // SparseConvBlock with conv1a/conv1b (normalized_channels < output_channels) or plain
     // conv1 (decoder blocks): net_definitions_torch.py:253-302.  `out` receives conv4.
-    int block(const std::string& name, Feat in, const GridDev& g, const float* imp, bool with_imp,
+    int block(const std::string& name, Feat in, const NbList& l, const float* imp, bool with_imp,
               Feat out, float** out_imp, bool out_f32 = false) {
         asr_hip_context* c = ctx;
         int C = out.c;
-        float* t1 = act(g.v, C);
-        float* t2 = act(g.v, C);
+        float* t1 = act(l.num_out, C);
+        float* t2 = act(l.num_out, C);
         if (!t1 || !t2) ASR_FAIL(c, ASR_HIP_EHIP, "arena allocation failed");
         int ca_ = 0, cb_ = 0;
         float* oi_ = nullptr;
@@ -1221,45 +1198,37 @@ struct Net {
             ASR_TRY(cout_of(name + ".conv1a", &ca_));
             ASR_TRY(cout_of(name + ".conv1b", &cb_));
             if (ca_ + cb_ != C) ASR_FAIL(c, ASR_HIP_EWEIGHT, "%s: conv1a+conv1b != block width", name.c_str());
-            oi_ = arena_alloc<float>(c->scratch, g.v);
+            oi_ = arena_alloc<float>(c->scratch, l.num_out);
             if (!oi_) ASR_FAIL(c, ASR_HIP_EHIP, "arena allocation failed");
         }
         // t1 is written twice (conv1, conv3): one running maximum per use
         Feat f1{t1, C, C, new_amax()}, f2{t2, C, C, new_amax()}, f3{t1, C, C, new_amax()};
         if (with_imp) {
-            ASR_TRY(conv_ab(name, 55, in, g.nidx, g.nkidx, g.nrs, g.perm_nb, g.v, g.v, imp, t1, C, ca_, cb_, oi_, f1.amax));
+            ASR_TRY(conv_ab(name, in, l, imp, t1, C, ca_, cb_, oi_, f1.amax));
             *out_imp = oi_;
         } else {
-            ASR_TRY(conv(name + ".conv1", 55, in, g.nidx, g.nkidx, g.nrs, g.perm_nb, g.v, g.v, nullptr, 0, t1, C,
-                         C, nullptr, nullptr, 0, false, f1.amax));
+            ASR_TRY(conv(name + ".conv1", in, l, nullptr, 0, t1, C, C, nullptr, nullptr, 0, false, f1.amax));
         }
-        ASR_TRY(conv(name + ".conv2", 55, f1, g.nidx, g.nkidx, g.nrs, g.perm_nb, g.v, g.v, nullptr, 0, t2, C, C,
-                     nullptr, nullptr, 0, false, f2.amax));
-        ASR_TRY(conv(name + ".conv3", 55, f2, g.nidx, g.nkidx, g.nrs, g.perm_nb, g.v, g.v, nullptr, 0, t1, C, C,
-                     nullptr, nullptr, 0, false, f3.amax));
-        ASR_TRY(conv(name + ".conv4", 55, f3, g.nidx, g.nkidx, g.nrs, g.perm_nb, g.v, g.v, nullptr, 0, out.p,
-                     out.ld, C, nullptr, nullptr, 0, out_f32, out.amax));
+        ASR_TRY(conv(name + ".conv2", f1, l, nullptr, 0, t2, C, C, nullptr, nullptr, 0, false, f2.amax));
+        ASR_TRY(conv(name + ".conv3", f2, l, nullptr, 0, t1, C, C, nullptr, nullptr, 0, false, f3.amax));
+        ASR_TRY(conv(name + ".conv4", f3, l, nullptr, 0, out.p, out.ld, C, nullptr, nullptr, 0, out_f32, out.amax));
         return ASR_HIP_OK;
     }
-    // SparseConvTransitionBlock down (conv1a/conv1b): net_definitions_torch.py:357-387
-    int down(const std::string& name, Feat in, const GridDev& fine, const GridDev& coarse,
-             const float* imp, Feat out, float** out_imp) {
+    // SparseConvTransitionBlock down (conv1a/conv1b) over a down list: net_definitions_torch.py:357-387
+    int down(const std::string& name, Feat in, const NbList& l, const float* imp, Feat out, float** out_imp) {
         int ca, cb;
         ASR_TRY(cout_of(name + ".conv1a", &ca));
         ASR_TRY(cout_of(name + ".conv1b", &cb));
         if (ca + cb != out.c) ASR_FAIL(ctx, ASR_HIP_EWEIGHT, "%s: conv1a+conv1b != width", name.c_str());
-        float* oi = arena_alloc<float>(ctx->scratch, coarse.v);
+        float* oi = arena_alloc<float>(ctx->scratch, l.num_out);
         if (!oi) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-        ASR_TRY(conv_ab(name, 9, in, fine.down_idx, fine.down_kidx, fine.down_rs, fine.perm_down, coarse.v, fine.v,
-                        imp, out.p, out.ld, ca, cb, oi, out.amax));
+        ASR_TRY(conv_ab(name, in, l, imp, out.p, out.ld, ca, cb, oi, out.amax));
         *out_imp = oi;
         return ASR_HIP_OK;
     }
-    // up transition (conv1): rows = fine voxels, inputs from the coarse grid
-    int up(const std::string& name, Feat in, const GridDev& fine, const GridDev& coarse, Feat out,
-           const float* residual, i64 residual_ld) {
-        return conv(name + ".conv1", 9, in, fine.up_idx, fine.up_kidx, fine.up_rs, fine.perm_up, fine.v, coarse.v,
-                    nullptr, 0, out.p, out.ld, out.c, nullptr, residual, residual_ld, false, out.amax);
+    // up transition (conv1) over an up list: rows = fine voxels, inputs from the coarse grid
+    int up(const std::string& name, Feat in, const NbList& l, Feat out, const float* residual, i64 residual_ld) {
+        return conv(name + ".conv1", in, l, nullptr, 0, out.p, out.ld, out.c, nullptr, residual, residual_ld, false, out.amax);
     }
 };
 
@@ -1297,55 +1266,26 @@ namespace {
 // the step runs beside the continuous conv); plans land in `on`'s persist arena, the orders in the arrays implicit_build
 // allocated.
 int build_tilings_and_plans(asr_hip_context* ctx, asr_hip_context* on, int precision) {
+    // The plan batch takes the table's order (its headers hold positions in one shared pool).  The regrouping keeps the order
+    // it has always had, the 9-slot lists first: its sorts see the lists concatenated in job order.
     std::vector<asr_row_group_job> rg_jobs;
-    for (int i = 0; i + 1 < ASR_NUM_GRIDS; ++i) {
-        GridDev& g = ctx->grids[i];
-        rg_jobs.push_back({g.up_kidx, g.up_rs, g.v, 9, g.perm_up});
-        rg_jobs.push_back({g.down_kidx, g.down_rs, ctx->grids[i + 1].v, 9, g.perm_down});
-    }
-    for (int i = 0; i < ASR_NUM_GRIDS; ++i) {
-        GridDev& g = ctx->grids[i];
-        rg_jobs.push_back({g.nkidx, g.nrs, g.v, 55, g.perm_nb});
-    }
+    for (int wide = 0; wide < 2; ++wide)
+        for (NbList& l : ctx->lists)
+            if ((l.kind == NbList::SAME) == (wide != 0))
+                rg_jobs.push_back({l.kidx, l.rs, l.num_out, l.K, const_cast<int32_t*>(l.perm)});
     on->scratch.reset();
     if (asr_geom_row_groups_batch(on, rg_jobs.data(), (int)rg_jobs.size(), ASR_ROW_GROUP_SEGMENT) != ASR_HIP_OK) {
         if (on != ctx) ctx->err = on->err;
         return ASR_HIP_EHIP;
     }
     if (precision != 0 && ctx->opt.sconv_plan) {
-        struct Job {
-            const int32_t* idx;
-            const uint8_t* kidx;
-            const i64* rs;
-            const int32_t* perm;
-            i64 rows;
-            int K;
-        };
-        std::vector<Job> jobs;
-        for (int i = 0; i < ASR_NUM_GRIDS; ++i) {
-            GridDev& g = ctx->grids[i];
-            jobs.push_back({g.nidx, g.nkidx, g.nrs, g.perm_nb, g.v, 55});
-            if (i + 1 < ASR_NUM_GRIDS) {
-                GridDev& c = ctx->grids[i + 1];
-                jobs.push_back({g.up_idx, g.up_kidx, g.up_rs, g.perm_up, g.v, 9});
-                jobs.push_back({g.down_idx, g.down_kidx, g.down_rs, g.perm_down, c.v, 9});
-            }
-        }
-        std::vector<asr_conv_plan> plans(jobs.size());
-        for (size_t j = 0; j < jobs.size(); ++j) {
-            plans[j].nidx = jobs[j].idx;
-            plans[j].kidx = jobs[j].kidx;
-            plans[j].rs = jobs[j].rs;
-            plans[j].perm = jobs[j].perm;
-            plans[j].num_out = jobs[j].rows;
-            plans[j].K = jobs[j].K;
-        }
-        const int rc = asr_geom_conv_plan_batch(on, on->persist, plans.data(), (int)plans.size());
+        asr_conv_plan* plans[ASR_NUM_LISTS];
+        for (NbList& l : ctx->lists) plans[l.id] = &l;
+        const int rc = asr_geom_conv_plan_batch(on, on->persist, plans, ASR_NUM_LISTS);
         if (rc != ASR_HIP_OK) {
             if (on != ctx) ctx->err = on->err;
             return rc;
         }
-        for (size_t j = 0; j < jobs.size(); ++j) ctx->conv_plans[jobs[j].rs] = plans[j];
     }
     return ASR_HIP_OK;
 }
@@ -1387,7 +1327,7 @@ int build_begin(asr_hip_context* ctx, i64 n, const asr_implicit_params* prm) {
     ctx->has_search = false;
     ctx->build_sharded = false;
     ctx->build_mark_ok = false;
-    ctx->conv_plans.clear();
+    ctx->reset_lists();
     memset(&ctx->sizes, 0, sizeof(ctx->sizes));
     ctx->sizes.num_points = n;
     if (asr_octree_frame_init(&ctx->frame, prm->bb_min, prm->bb_max) != ASR_HIP_OK)
@@ -1407,6 +1347,19 @@ int build_level0(asr_hip_context* ctx) {
     if (!g0.centers || !g0.sizes) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
     return asr_geom_voxel_info(ctx, &ctx->frame, g0.keys, g0.v, g0.centers, g0.sizes);
 }
+// a list's arrays, once its builder has made them and both of its grids exist; its tiling order is allocated here and
+// filled by build_tilings_and_plans
+int set_list(asr_hip_context* ctx, NbList& l, const int32_t* idx, const uint8_t* kidx, const i64* rs, i64 pairs) {
+    l.nidx = idx;
+    l.kidx = kidx;
+    l.rs = rs;
+    l.pairs = pairs;
+    l.num_out = ctx->grids[l.lvl_out].v;
+    l.num_inp = ctx->grids[l.lvl_in].v;
+    l.perm = arena_alloc<int32_t>(ctx->persist, l.num_out);
+    if (!l.perm) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    return ASR_HIP_OK;
+}
 // key sets of the coarser grids with their up / down lists: a chain of four small coarsening steps
 // (cpp/lib/grid.cpp:245-314; CombineSiblings + neighbors_down = invert(up lists), net_definitions_torch.py:548-559)
 int build_coarse_grids(asr_hip_context* ctx) {
@@ -1415,20 +1368,13 @@ int build_coarse_grids(asr_hip_context* ctx) {
         g = GridDev();
         ctx->scratch.reset();
         GridDev& prev = ctx->grids[i - 1];
-        ASR_TRY(asr_geom_coarsen_build(ctx, ctx->persist, prev.keys, prev.v, &g.keys, &g.v, &prev.up_idx,
-                                       &prev.up_kidx, &prev.up_rs, &prev.down_idx, &prev.down_kidx, &prev.down_rs));
-        prev.perm_up = arena_alloc<int32_t>(ctx->persist, prev.v);
-        prev.perm_down = arena_alloc<int32_t>(ctx->persist, g.v);
-        if (!prev.perm_up || !prev.perm_down) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-        std::string s = std::to_string(i - 1);
-        name_it(ctx, "up_neighbors_index" + s, prev.up_idx, 4 * prev.v);
-        name_it(ctx, "up_neighbors_kernel_index" + s, prev.up_kidx, prev.v);
-        name_it(ctx, "up_neighbors_row_splits" + s, prev.up_rs, 8 * (prev.v + 1));
-        name_it(ctx, "down_neighbors_index" + s, prev.down_idx, 4 * prev.v);
-        name_it(ctx, "down_neighbors_kernel_index" + s, prev.down_kidx, prev.v);
-        name_it(ctx, "down_neighbors_row_splits" + s, prev.down_rs, 8 * (g.v + 1));
-        name_it(ctx, "tiling_up" + s, prev.perm_up, 4 * prev.v);
-        name_it(ctx, "tiling_down" + s, prev.perm_down, 4 * g.v);
+        int32_t *up_idx, *down_idx;
+        uint8_t *up_kidx, *down_kidx;
+        i64 *up_rs, *down_rs;
+        ASR_TRY(asr_geom_coarsen_build(ctx, ctx->persist, prev.keys, prev.v, &g.keys, &g.v, &up_idx, &up_kidx, &up_rs,
+                                       &down_idx, &down_kidx, &down_rs));
+        ASR_TRY(set_list(ctx, ctx->up(i - 1), up_idx, up_kidx, up_rs, prev.v));  // one entry per fine voxel
+        ASR_TRY(set_list(ctx, ctx->down(i - 1), down_idx, down_kidx, down_rs, prev.v));
         g.centers = arena_alloc<float>(ctx->persist, 3 * g.v);
         g.sizes = arena_alloc<float>(ctx->persist, g.v);
         if (!g.centers || !g.sizes) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
@@ -1436,22 +1382,25 @@ int build_coarse_grids(asr_hip_context* ctx) {
     }
     return ASR_HIP_OK;
 }
-// tiling-order arrays + the names of the per-grid arrays, once the 55-slot lists exist
+// the names of the per-grid arrays and of the lists, once all of them exist
 int build_grid_names(asr_hip_context* ctx) {
     for (int i = 0; i < ASR_NUM_GRIDS; ++i) {
         GridDev& g = ctx->grids[i];
-        g.perm_nb = arena_alloc<int32_t>(ctx->persist, g.v);
-        if (!g.perm_nb) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
         ctx->sizes.num_voxels[i] = g.v;
-        ctx->sizes.num_pairs[i] = g.p;
+        ctx->sizes.num_pairs[i] = ctx->same(i).pairs;
         std::string s = std::to_string(i);
         name_it(ctx, "voxel_keys" + s, g.keys, 8 * g.v);
         name_it(ctx, "voxel_centers" + s, g.centers, 12 * g.v);
         name_it(ctx, "voxel_sizes" + s, g.sizes, 4 * g.v);
-        name_it(ctx, "neighbors_index" + s, g.nidx, 4 * g.p);
-        name_it(ctx, "neighbors_kernel_index" + s, g.nkidx, g.p);
-        name_it(ctx, "neighbors_row_splits" + s, g.nrs, 8 * (g.v + 1));
-        name_it(ctx, "tiling" + s, g.perm_nb, 4 * g.v);
+    }
+    static const char* const kind[3] = {"", "up_", "down_"};
+    static const char* const tiling[3] = {"tiling", "tiling_up", "tiling_down"};
+    for (const NbList& l : ctx->lists) {
+        std::string s = std::to_string(l.id / 3), nb = std::string(kind[l.kind]) + "neighbors_";  // numbered by the finer grid
+        name_it(ctx, nb + "index" + s, l.nidx, 4 * l.pairs);
+        name_it(ctx, nb + "kernel_index" + s, l.kidx, l.pairs);
+        name_it(ctx, nb + "row_splits" + s, l.rs, 8 * (l.num_out + 1));
+        name_it(ctx, tiling[l.kind] + s, l.perm, 4 * l.num_out);
     }
     return ASR_HIP_OK;
 }
@@ -1642,20 +1591,14 @@ int implicit_build(asr_hip_context* ctx, const float* points, const float* radii
             }
         }
         ASR_TRY(asr_geom_neighbors_build_batch(ctx, ctx->persist, nb, ASR_NUM_GRIDS));
-        for (int i = 0; i < ASR_NUM_GRIDS; ++i) {
-            GridDev& g = ctx->grids[i];
-            g.nrs = nb[i].rs;
-            g.nidx = nb[i].idx;
-            g.nkidx = nb[i].kidx;
-            g.p = nb[i].p;
-        }
+        for (int i = 0; i < ASR_NUM_GRIDS; ++i) ASR_TRY(set_list(ctx, ctx->same(i), nb[i].idx, nb[i].kidx, nb[i].rs, nb[i].p));
     }
     ASR_TRY(build_grid_names(ctx));
     // MFMA tiling orders + row-group plans.  (Deferring them to the auxiliary stream beside the continuous conv of the network
     // half -- only the U-Net needs them -- was measured again in round 4: geometry wall 9.5 -> 8.5-8.9 ms, network wall + 1.2 ms.)
-    if (st) {  // tiling orders of all rows; the plans are this rank's (asr_shard_lists)
+    if (st) {  // tiling orders of all rows; the plans are this rank's (asr_shard_halos)
         ASR_TRY(build_tilings_and_plans(ctx, ctx, 0));
-        ASR_TRY(asr_shard_lists(ctx, st, prm->precision != 0 && ctx->opt.sconv_plan));
+        ASR_TRY(asr_shard_halos(ctx, st, prm->precision != 0 && ctx->opt.sconv_plan));
     } else {
         ASR_TRY(build_tilings_and_plans(ctx, ctx, prm->precision));
     }
@@ -1819,29 +1762,29 @@ int network_unet_decode(asr_hip_context* ctx, Net& net, const asr_implicit_param
         ASR_TRY(asr_conv16_convert(ctx, feats1, V0 * (i64)C0, feats1_in, 1));
     }
     Feat f_in{feats1_in, C0, C0, feats_amax};
-    ASR_TRY(net.block("sparseconv_encblock0", f_in, g[0], imp_pairs, true, enc_out[0], &imp));
+    ASR_TRY(net.block("sparseconv_encblock0", f_in, ctx->same(0), imp_pairs, true, enc_out[0], &imp));
     for (int i = 1; i <= 4; ++i) {
         std::string dn = "sparseconv_down" + std::to_string(i < 4 ? i : 3);
         float* t = buf(g[i].v, c_down[i]);
         if (!t) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
         float* imp_d = nullptr;
         const Feat ft{t, c_down[i], c_down[i], net.new_amax()};
-        ASR_TRY(net.down(dn, enc_out[i - 1], g[i - 1], g[i], imp, ft, &imp_d));
+        ASR_TRY(net.down(dn, enc_out[i - 1], ctx->down(i - 1), imp, ft, &imp_d));
         float* imp_e = nullptr;
-        ASR_TRY(net.block("sparseconv_encblock" + std::to_string(i), ft, g[i], imp_d, true, enc_out[i], &imp_e));
+        ASR_TRY(net.block("sparseconv_encblock" + std::to_string(i), ft, ctx->same(i), imp_d, true, enc_out[i], &imp_e));
         imp = imp_e;
     }
     // decoder
     Feat cur = enc_out[4];
     for (int i = 3; i >= 1; --i) {
-        ASR_TRY(net.up("sparseconv_up" + std::to_string(i), cur, g[i], g[i + 1],
-                       Feat{cat[i], cat_ld[i], c_up[i], cat_amax[i]}, nullptr, 0));
+        ASR_TRY(net.up("sparseconv_up" + std::to_string(i), cur, ctx->up(i), Feat{cat[i], cat_ld[i], c_up[i], cat_amax[i]},
+                       nullptr, 0));
         float* d = buf(g[i].v, c_dec[i]);
         if (!d) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
         float* dummy = nullptr;
         const Feat fd{d, c_dec[i], c_dec[i], net.new_amax()};
         ASR_TRY(net.block("sparseconv_decblock" + std::to_string(i), Feat{cat[i], cat_ld[i], cat_ld[i], cat_amax[i]},
-                          g[i], nullptr, false, fd, &dummy));
+                          ctx->same(i), nullptr, false, fd, &dummy));
         cur = fd;
     }
     if (c_up[0] != c_enc[0])
@@ -1851,10 +1794,10 @@ int network_unet_decode(asr_hip_context* ctx, Net& net, const asr_implicit_param
     if (!f21 || !code) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
     // feats21 = relu(up0(feats19)) + feats2   (net_definitions_torch.py:631-633)
     const Feat ff21{f21, c_up[0], c_up[0], net.new_amax()};
-    ASR_TRY(net.up("sparseconv_up0", cur, g[0], g[1], ff21, f2, c_enc[0]));
+    ASR_TRY(net.up("sparseconv_up0", cur, ctx->up(0), ff21, f2, c_enc[0]));
     {
         float* dummy = nullptr;
-        ASR_TRY(net.block("sparseconv_decblock0", ff21, g[0], nullptr, false,
+        ASR_TRY(net.block("sparseconv_decblock0", ff21, ctx->same(0), nullptr, false,
                           Feat{code, c_dec[0], c_dec[0]}, &dummy, true));  // `code` is f32 in every mode
     }
     ctx->code = code;

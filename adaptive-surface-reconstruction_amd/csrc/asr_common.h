@@ -75,25 +75,11 @@ static inline void arena_rewind(Arena& a, const ArenaMark& m) {
 }
 
 struct GridDev {
-    i64 v = 0, p = 0;
+    i64 v = 0;
     u64* keys = nullptr;
     float* centers = nullptr;
     float* sizes = nullptr;
-    int32_t* nidx = nullptr;
-    uint8_t* nkidx = nullptr;
-    i64* nrs = nullptr;
-    int32_t* up_idx = nullptr;
-    uint8_t* up_kidx = nullptr;
-    i64* up_rs = nullptr;
-    // inverted up lists (rows = next coarser grid)
-    int32_t* down_idx = nullptr;
-    uint8_t* down_kidx = nullptr;
-    i64* down_rs = nullptr;
-    // MFMA tiling orders (asr_geom_row_groups) of the three CSRs whose rows live on this grid
-    int32_t* perm_nb = nullptr;    // rows = this grid (55-slot lists)
-    int32_t* perm_up = nullptr;    // rows = this grid (up lists, inputs from the coarser grid)
-    int32_t* perm_down = nullptr;  // rows = next coarser grid (inverted up lists)
-};
+};  // its neighbour lists: asr_hip_context::same / up / down
 
 // Tunables of one context (asr_hip_context_set_option); the defaults can also be seeded from the
 // environment (ASR_SCONV_MIN_BLOCKS, ...) when the context is created, for experiments.
@@ -141,20 +127,33 @@ struct asr_conv_plan_view {
     i64 groups;            // ceil(num_out / 16)
     unsigned pool_bytes;
 };
-struct asr_conv_plan {
+// the rows a convolution computes: a neighbour list and the order its rows are tiled in
+struct asr_conv_rows {
+    const int32_t* nidx = nullptr;
+    const uint8_t* kidx = nullptr;
+    const i64* rs = nullptr;
+    const int32_t* perm = nullptr;  // tiling order (asr_geom_row_groups): num_out rows of the list, or null
+    i64 num_out = 0;
+    int K = 0;
+};
+// ... and their plan (hdr == nullptr: none was built)
+struct asr_conv_plan : asr_conv_rows {
     uint4* hdr = nullptr;
     int32_t* pool = nullptr;
     i64 groups = 0, groups_pad = 0, blocks = 0;
     i64* offs = nullptr;  // [groups_pad + 1] first pool block of every group; offs[groups_pad] = blocks (device)
-    // the list it was built from
-    const int32_t* nidx = nullptr;
-    const uint8_t* kidx = nullptr;
-    const i64* rs = nullptr;
-    const int32_t* perm = nullptr;
-    i64 num_out = 0;
-    int K = 0;
     bool usable() const { return hdr && blocks * 64 < (i64(1) << 32) - 65536; }
     asr_conv_plan_view view() const { return {hdr, pool, groups, (unsigned)(blocks * 64)}; }
+};
+// One of the 13 neighbour lists of a grid hierarchy, with the plan of ALL its rows.  Grid i has a 55-slot list over itself
+// (same), a 9-slot list that reads the next coarser grid (up) and that list inverted (down: its rows are grid i + 1).
+constexpr int ASR_NUM_LISTS = 3 * ASR_NUM_GRIDS - 2;
+struct NbList : asr_conv_plan {
+    enum Kind { SAME, UP, DOWN };
+    int id = 0;  // position in asr_hip_context::lists
+    Kind kind = SAME;
+    int lvl_out = 0, lvl_in = 0;  // grid of the rows, grid of the inputs
+    i64 num_inp = 0, pairs = 0;
 };
 
 // Points of the last implicit_build in Morton order (asr_geom_presort): shared by the octree insertion (neighbouring
@@ -195,7 +194,6 @@ struct asr_hip_context {
     hipEvent_t switch_ev = nullptr;  // asr_hip_context_set_stream: recorded on the old stream, awaited by the new one
     std::string err;
     AsrOptions opt;
-    std::map<const void*, asr_conv_plan> conv_plans;  // row splits pointer -> plan of that list (implicit_build)
     std::map<std::string, i64> sconv_launches;  // "NT,KC,IMP,WAVES,DUAL" -> launches (asr_hip_sparse_conv_variant_counts)
     ArenaMark build_mark;                         // persist arena right after implicit_build
     bool build_mark_ok = false;
@@ -211,6 +209,21 @@ struct asr_hip_context {
     asr_octree_frame frame;
     asr_implicit_sizes sizes;
     GridDev grids[ASR_NUM_GRIDS];
+    NbList lists[ASR_NUM_LISTS];  // per grid i: same(i), up(i), down(i) -- the last grid has no coarser one
+    NbList& same(int i) { return lists[3 * i]; }
+    NbList& up(int i) { return lists[3 * i + 1]; }
+    NbList& down(int i) { return lists[3 * i + 2]; }
+    asr_hip_context() { reset_lists(); }
+    void reset_lists() {  // what every build starts with: no arrays, no plans
+        for (int j = 0; j < ASR_NUM_LISTS; ++j) {
+            NbList& l = lists[j] = NbList();
+            l.id = j;
+            l.kind = NbList::Kind(j % 3);
+            l.K = l.kind == NbList::SAME ? 55 : 9;
+            l.lvl_out = j / 3 + (l.kind == NbList::DOWN);
+            l.lvl_in = j / 3 + (l.kind == NbList::UP);
+        }
+    }
     int32_t* agg_idx = nullptr;
     float* agg_dist = nullptr;
     float* agg_compat = nullptr;
@@ -416,7 +429,7 @@ int asr_shard_build(asr_hip_context* ctx, const asr_shard_comm* comm, int want_p
 int asr_shard_ownership(asr_hip_context* ctx, const asr_shard_comm* comm, int by_pairs, asr_shard_state** out);
 int asr_shard_ownership_coarser(asr_hip_context* ctx, asr_shard_state* st);
 const int32_t* asr_shard_owner(const asr_shard_state* st, int level);
-int asr_shard_lists(asr_hip_context* ctx, asr_shard_state* st, int want_plans);
+int asr_shard_halos(asr_hip_context* ctx, asr_shard_state* st, int want_plans);
 const int32_t* asr_shard_level_rows(const asr_shard_state* st, int level, i64* n);
 int asr_shard_query_rows(asr_hip_context* ctx, const asr_shard_state* st, i64 prefix, Arena& keep, int32_t** rows_out,
                          i64* n_out);
@@ -428,8 +441,9 @@ const asr_shard_stats* asr_shard_get_stats(const asr_shard_state* st);
 // all ranks learn whether ANY rank failed so far (one MAX all-reduce of a status word): rc_local when this rank failed,
 // ASR_HIP_EPEER when only others did, ASR_HIP_OK when nobody did
 int asr_shard_agree(asr_hip_context* ctx, const asr_shard_comm* comm, int rc_local, const char* phase);
-int asr_shard_before_conv(asr_hip_context* ctx, asr_shard_state* st, const void* rs, void* feat, i64 ld_bytes, i64 row_bytes,
-                          float* imp, unsigned* in_amax, const int32_t** perm, i64* num_out, const asr_conv_plan** plan);
+// before a convolution over `list`: the halo exchange of its input; *rows = the rows this rank computes, with their plan
+int asr_shard_before_conv(asr_hip_context* ctx, asr_shard_state* st, const NbList& list, void* feat, i64 ld_bytes,
+                          i64 row_bytes, float* imp, unsigned* in_amax, const asr_conv_plan** rows);
 int asr_shard_stitch(asr_hip_context* ctx, asr_shard_state* st, float* values);
 const int32_t* asr_shard_owned_rows0(const asr_shard_state* st, i64* n);  // grid-0 rows of this rank, ascending (world > 1)
 
@@ -584,8 +598,8 @@ int asr_conv_sparse(asr_hip_context* ctx, const asr_sparse_conv_args* args);
 int asr_geom_conv_plan_count(asr_hip_context* ctx, Arena& keep, const int32_t* nidx, const uint8_t* kidx, const i64* rs,
                              const int32_t* perm, i64 num_out, int K, asr_conv_plan* plan);
 int asr_geom_conv_plan_fill(asr_hip_context* ctx, Arena& keep, asr_conv_plan* plan, i64 blocks);
-// plans[j] with nidx/kidx/rs/perm/num_out/K set: all built in one pass over the concatenated lists, one pool
-int asr_geom_conv_plan_batch(asr_hip_context* ctx, Arena& keep, asr_conv_plan* plans, int n);
+// *plans[j] with nidx/kidx/rs/perm/num_out/K set: all built in one pass over the concatenated lists, one pool
+int asr_geom_conv_plan_batch(asr_hip_context* ctx, Arena& keep, asr_conv_plan* const* plans, int n);
 int asr_geom_conv_plan_build(asr_hip_context* ctx, Arena& keep, const int32_t* nidx, const uint8_t* kidx, const i64* rs,
                              const int32_t* perm, i64 num_out, int K, asr_conv_plan* plan);  // count + read-back + fill
 

@@ -4270,7 +4270,7 @@ __global__ void k_plan_fill_batch(PlanBatch b, const i64* __restrict__ offs, uin
 }
 }  // namespace
 
-int asr_geom_conv_plan_batch(asr_hip_context* ctx, Arena& keep, asr_conv_plan* plans, int n) {
+int asr_geom_conv_plan_batch(asr_hip_context* ctx, Arena& keep, asr_conv_plan* const* plans, int n) {
     if (n > PLAN_MAX_JOBS) ASR_FAIL(ctx, ASR_HIP_EINVAL, "conv_plan_batch: too many lists");
     PlanBatch b;
     memset(&b, 0, sizeof(b));
@@ -4278,7 +4278,7 @@ int asr_geom_conv_plan_batch(asr_hip_context* ctx, Arena& keep, asr_conv_plan* p
     i64 total = 0;
     int which[PLAN_MAX_JOBS];
     for (int j = 0; j < n; ++j) {
-        asr_conv_plan& pl = plans[j];
+        asr_conv_plan& pl = *plans[j];
         pl.hdr = nullptr;
         pl.pool = nullptr;
         pl.offs = nullptr;
@@ -4315,7 +4315,7 @@ int asr_geom_conv_plan_batch(asr_hip_context* ctx, Arena& keep, asr_conv_plan* p
     k_plan_fill_batch<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, offs, hdr, pool);
     ASR_CHECK_LAUNCH(ctx);
     for (int t = 0; t < b.n; ++t) {
-        asr_conv_plan& pl = plans[which[t]];
+        asr_conv_plan& pl = *plans[which[t]];
         pl.hdr = hdr + b.base[t] / 16;
         pl.offs = offs + b.base[t] / 16;
         pl.pool = pool;

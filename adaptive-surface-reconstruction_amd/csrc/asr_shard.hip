@@ -20,7 +20,6 @@
 #include <cstring>
 #include <algorithm>
 #include <chrono>
-#include <map>
 #include <vector>
 
 #include <rocprim/rocprim.hpp>
@@ -79,18 +78,17 @@ __global__ void k_shard_owner_by_count(const int32_t* order, i64 v, int world, i
     owner[order[i]] = (int32_t)(o > world - 1 ? world - 1 : o);
 }
 // ---- all neighbour lists of the hierarchy in one pass each (a rank's forward paid ~330 tiny launches for the per-list form) ----
-constexpr int SHARD_LISTS = 3 * ASR_NUM_GRIDS - 2;
 struct ShardBatch {
     int n, world, me;
-    i64 out_off[SHARD_LISTS + 1];  // prefix sums of the lists' row counts
-    i64 in_off[SHARD_LISTS + 1];   // prefix sums of world * (input rows)
-    const int32_t* perm[SHARD_LISTS];
-    const int32_t* idx[SHARD_LISTS];
-    const i64* rs[SHARD_LISTS];
-    const int32_t* owner_out[SHARD_LISTS];
-    const int32_t* owner_in[SHARD_LISTS];
-    i64 v_in[SHARD_LISTS];
-    int symmetric[SHARD_LISTS];
+    i64 out_off[ASR_NUM_LISTS + 1];  // prefix sums of the lists' row counts
+    i64 in_off[ASR_NUM_LISTS + 1];   // prefix sums of world * (input rows)
+    const int32_t* perm[ASR_NUM_LISTS];
+    const int32_t* idx[ASR_NUM_LISTS];
+    const i64* rs[ASR_NUM_LISTS];
+    const int32_t* owner_out[ASR_NUM_LISTS];
+    const int32_t* owner_in[ASR_NUM_LISTS];
+    i64 v_in[ASR_NUM_LISTS];
+    int symmetric[ASR_NUM_LISTS];
 };
 __device__ __forceinline__ int shard_list_of(const i64* off, int n, i64 t) {  // the j with off[j] <= t < off[j + 1]
     int j = 0;
@@ -284,10 +282,7 @@ static int shard_sort_u32(asr_hip_context* ctx, const int32_t* in, int32_t* out,
 
 // halo of one neighbour list: rows of the INPUT buffer, concatenated per peer (ascending peer, ascending row)
 struct ShardCsr {
-    const int32_t* perm = nullptr;  // owned output rows in the list's tiling order
-    i64 num_out = 0;
-    asr_conv_plan plan;
-    bool has_plan = false;
+    asr_conv_plan rows;  // the list with perm / num_out = the owned output rows in its tiling order, and the plan of those
     const int32_t* send_rows = nullptr;
     const int32_t* recv_rows = nullptr;
     std::vector<int> send_peer, recv_peer;  // peers with a non-empty message
@@ -296,7 +291,7 @@ struct ShardCsr {
 struct asr_shard_state {
     asr_shard_comm comm;
     int rank = 0, world = 1;
-    std::map<const void*, ShardCsr> csr;  // keyed by the list's row-splits pointer
+    ShardCsr csr[ASR_NUM_LISTS];  // by NbList::id
     int32_t* owner[ASR_NUM_GRIDS] = {};
     bool owned_lists = false;  // sharded geometry: the 55-slot lists hold the owned rows only (halo by symmetry)
     int32_t* level_rows[ASR_NUM_GRIDS] = {};  // sharded geometry: owned rows per level, ascending
@@ -336,30 +331,6 @@ void asr_shard_release(asr_hip_context* ctx) {
 }
 
 const asr_shard_stats* asr_shard_get_stats(const asr_shard_state* st) { return &st->stats; }
-
-// the 13 neighbour lists of the hierarchy: (rows-level, input-level, arrays)
-namespace {
-struct ListRef {
-    const int32_t* idx;
-    const uint8_t* kidx;
-    const i64* rs;
-    const int32_t* perm;
-    i64 v_out, v_in;
-    int lvl_out, lvl_in, K;
-};
-std::vector<ListRef> shard_lists(asr_hip_context* ctx) {
-    std::vector<ListRef> L;
-    GridDev* g = ctx->grids;
-    for (int i = 0; i < ASR_NUM_GRIDS; ++i) {
-        L.push_back({g[i].nidx, g[i].nkidx, g[i].nrs, g[i].perm_nb, g[i].v, g[i].v, i, i, 55});
-        if (i + 1 < ASR_NUM_GRIDS) {
-            L.push_back({g[i].up_idx, g[i].up_kidx, g[i].up_rs, g[i].perm_up, g[i].v, g[i + 1].v, i, i + 1, 9});
-            L.push_back({g[i].down_idx, g[i].down_kidx, g[i].down_rs, g[i].perm_down, g[i + 1].v, g[i].v, i + 1, i, 9});
-        }
-    }
-    return L;
-}
-}  // namespace
 
 // ownership of the voxels of the five grids.  by_pairs: equal numbers of neighbour pairs per rank (the 55-slot list of grid
 // 0 exists); else equal voxel counts (sharded geometry: ownership is decided BEFORE any list exists), and the owned rows of
@@ -416,7 +387,7 @@ int asr_shard_ownership(asr_hip_context* ctx, const asr_shard_comm* comm, int by
         const int low = ctx->leaf_lmax >= 0 ? 3 * (ASR_MAX_LEVEL - std::min(ctx->leaf_lmax, ASR_MAX_LEVEL)) : 0;
         ASR_TRY((sort_pairs<u64, int32_t>(ctx, ctx->scratch, codes, codes_s, ids, order, V0, 63, low)));
         if (by_pairs) {
-            k_shard_weights<<<grid_for(V0, BLK), BLK, 0, ctx->stream>>>(order, g[0].nrs, V0, w);
+            k_shard_weights<<<grid_for(V0, BLK), BLK, 0, ctx->stream>>>(order, ctx->same(0).rs, V0, w);
             ASR_CHECK_LAUNCH(ctx);
             size_t tb = 0;
             ASR_HIP_CHECK(ctx, rocprim::inclusive_scan(nullptr, tb, w, cum, (size_t)V0, rocprim::plus<i64>(), ctx->stream));
@@ -431,7 +402,7 @@ int asr_shard_ownership(asr_hip_context* ctx, const asr_shard_comm* comm, int by
     }
     if (by_pairs) {
         for (int i = 0; i + 1 < ASR_NUM_GRIDS; ++i) {
-            k_shard_coarser<<<grid_for(g[i].v, BLK), BLK, 0, ctx->stream>>>(st->owner[i], g[i].up_idx, g[i].up_kidx, g[i].v,
+            k_shard_coarser<<<grid_for(g[i].v, BLK), BLK, 0, ctx->stream>>>(st->owner[i], ctx->up(i).nidx, ctx->up(i).kidx, g[i].v,
                                                                             st->owner[i + 1]);
             ASR_CHECK_LAUNCH(ctx);
         }
@@ -459,7 +430,7 @@ int asr_shard_ownership_coarser(asr_hip_context* ctx, asr_shard_state* st) {
     for (int i = 0; i + 1 < ASR_NUM_GRIDS; ++i) {
         st->owner[i + 1] = arena_alloc<int32_t>((*st->mem), g[i + 1].v);
         if (!st->owner[i + 1]) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-        k_shard_coarser<<<grid_for(g[i].v, BLK), BLK, 0, ctx->stream>>>(st->owner[i], g[i].up_idx, g[i].up_kidx, g[i].v,
+        k_shard_coarser<<<grid_for(g[i].v, BLK), BLK, 0, ctx->stream>>>(st->owner[i], ctx->up(i).nidx, ctx->up(i).kidx, g[i].v,
                                                                         st->owner[i + 1]);
         ASR_CHECK_LAUNCH(ctx);
     }
@@ -469,32 +440,24 @@ const int32_t* asr_shard_owner(const asr_shard_state* st, int level) { return st
 
 // the rest of the shard state once the neighbour lists and their tiling orders exist: owned rows in tiling order, plans,
 // halo lists, stitch lists
-int asr_shard_lists(asr_hip_context* ctx, asr_shard_state* st, int want_plans) {
+int asr_shard_halos(asr_hip_context* ctx, asr_shard_state* st, int want_plans) {
     GridDev* g = ctx->grids;
-    const std::vector<ListRef> L = shard_lists(ctx);
+    const NbList* L = ctx->lists;
     const int world = st->world, me = st->rank;
     const i64 V0 = g[0].v;
     if (world == 1) {  // everything is mine: the monolithic driver's own orders and plans
-        for (const ListRef& l : L) {
-            ShardCsr c;
-            c.perm = l.perm;
-            c.num_out = l.v_out;
-            auto it = ctx->conv_plans.find(l.rs);
-            if (it != ctx->conv_plans.end()) {
-                c.plan = it->second;
-                c.has_plan = true;
-            }
+        for (const NbList& l : ctx->lists) {
+            ShardCsr& c = st->csr[l.id];
+            c.rows = l;
             c.send_first.push_back(0);
             c.recv_first.push_back(0);
-            st->csr[l.rs] = c;
         }
         for (int i = 0; i < ASR_NUM_GRIDS; ++i) st->stats.owned_rows[i] = g[i].v;
         return ASR_HIP_OK;
     }
     ctx->scratch.reset();
     // ---- per list: owned rows in tiling order, halo lists (device passes first, ONE read-back of all sizes) ----
-    const int nl = (int)L.size();
-    if (nl != SHARD_LISTS) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "sharded forward: %d neighbour lists?", nl);
+    const int nl = ASR_NUM_LISTS;
     // device counters per list: see k_shard_bounds_batch; + the stitch offsets
     const int per = 6 + 2 * (world + 1);
     i64* d_cnt = arena_alloc<i64>(ctx->scratch, (size_t)nl * per + world + 1 + 3);
@@ -508,17 +471,17 @@ int asr_shard_lists(asr_hip_context* ctx, asr_shard_state* st, int want_plans) {
     B.out_off[0] = B.in_off[0] = 0;
     size_t cap = 0;  // a rank sends / receives an input row at most once per peer, and no more entries than the list has pairs
     for (int j = 0; j < nl; ++j) {
-        const ListRef& l = L[j];
-        B.out_off[j + 1] = B.out_off[j] + l.v_out;
-        B.in_off[j + 1] = B.in_off[j] + (i64)world * l.v_in;
+        const NbList& l = L[j];
+        B.out_off[j + 1] = B.out_off[j] + l.num_out;
+        B.in_off[j + 1] = B.in_off[j] + (i64)world * l.num_inp;
         B.perm[j] = l.perm;
-        B.idx[j] = l.idx;
+        B.idx[j] = l.nidx;
         B.rs[j] = l.rs;
         B.owner_out[j] = st->owner[l.lvl_out];
         B.owner_in[j] = st->owner[l.lvl_in];
-        B.v_in[j] = l.v_in;
-        B.symmetric[j] = st->owned_lists && l.K == 55 ? 1 : 0;
-        cap += std::min<size_t>((size_t)world * l.v_in, (size_t)std::max<i64>(l.K == 55 ? g[l.lvl_out].p : g[std::min(l.lvl_out, l.lvl_in)].v, 1));
+        B.v_in[j] = l.num_inp;
+        B.symmetric[j] = st->owned_lists && l.kind == NbList::SAME ? 1 : 0;
+        cap += std::min<size_t>((size_t)world * l.num_inp, (size_t)std::max<i64>(l.pairs, 1));
     }
     const i64 n_out = B.out_off[nl], n_in = B.in_off[nl];
     if (n_in >= (i64(1) << 31) || n_out >= (i64(1) << 31))
@@ -573,14 +536,14 @@ int asr_shard_lists(asr_hip_context* ctx, asr_shard_state* st, int want_plans) {
     // plans of the owned rows
     int32_t* send_all = sel_send;
     int32_t* recv_all = sel_recv;
-    std::vector<asr_conv_plan> plans;
-    std::vector<int> plan_of;
+    std::vector<asr_conv_plan*> plans;
     for (int j = 0; j < nl; ++j) {
-        const ListRef& l = L[j];
+        const NbList& l = L[j];
         const i64* c = &h_cnt[(size_t)j * per];
-        ShardCsr cs;
-        cs.perm = sel_perm + c[3];
-        cs.num_out = c[0];
+        ShardCsr& cs = st->csr[j];
+        static_cast<asr_conv_rows&>(cs.rows) = l;  // (not the plan: that one covers all rows)
+        cs.rows.perm = sel_perm + c[3];
+        cs.rows.num_out = c[0];
         const i64 ns = c[1], nr = c[2];
         if (ns > 0) cs.send_rows = send_all + c[4];
         if (nr > 0) cs.recv_rows = recv_all + c[5];
@@ -598,29 +561,11 @@ int asr_shard_lists(asr_hip_context* ctx, asr_shard_state* st, int want_plans) {
         }
         cs.send_first.push_back(ns);
         cs.recv_first.push_back(nr);
-        if (l.K == 55) st->stats.halo_rows_recv[l.lvl_out] = nr;
-        if (l.K == 55) st->stats.owned_rows[l.lvl_out] = cs.num_out;
-        st->csr[l.rs] = cs;
-        if (want_plans && cs.num_out > 0) {
-            asr_conv_plan pl;
-            pl.nidx = l.idx;
-            pl.kidx = l.kidx;
-            pl.rs = l.rs;
-            pl.perm = cs.perm;
-            pl.num_out = cs.num_out;
-            pl.K = l.K;
-            plans.push_back(pl);
-            plan_of.push_back(j);
-        }
+        if (l.kind == NbList::SAME) st->stats.halo_rows_recv[l.lvl_out] = nr;
+        if (l.kind == NbList::SAME) st->stats.owned_rows[l.lvl_out] = cs.rows.num_out;
+        if (want_plans && cs.rows.num_out > 0) plans.push_back(&cs.rows);
     }
-    if (!plans.empty()) {
-        ASR_TRY(asr_geom_conv_plan_batch(ctx, (*st->mem), plans.data(), (int)plans.size()));
-        for (size_t q = 0; q < plans.size(); ++q) {
-            ShardCsr& cs = st->csr[L[plan_of[q]].rs];
-            cs.plan = plans[q];
-            cs.has_plan = true;
-        }
-    }
+    if (!plans.empty()) ASR_TRY(asr_geom_conv_plan_batch(ctx, (*st->mem), plans.data(), (int)plans.size()));
     return ASR_HIP_OK;
 }
 
@@ -629,7 +574,7 @@ int asr_shard_build(asr_hip_context* ctx, const asr_shard_comm* comm, int want_p
     *out = nullptr;
     asr_shard_state* st = nullptr;
     ASR_TRY(asr_shard_ownership(ctx, comm, 1, &st));
-    const int rc = asr_shard_lists(ctx, st, want_plans);
+    const int rc = asr_shard_halos(ctx, st, want_plans);
     if (rc != ASR_HIP_OK) {
         asr_shard_free(st);
         return rc;
@@ -673,17 +618,13 @@ const int32_t* asr_shard_owned_rows0(const asr_shard_state* st, i64* n) {
 }
 int asr_shard_world(const asr_shard_state* st) { return st->world; }
 
-// before a convolution over the list `rs`: the rows it computes (perm, num_out, plan), the halo exchange of its input and
+// before a convolution over `list`: the rows it computes (perm, num_out, plan), the halo exchange of its input and
 // -- f16x2: in_amax, the running maximum the producers of the input buffer kept over the rows THEY wrote -- the maximum
 // over the ranks (the tensor's, as on one GPU), in the same group as the exchange where the transport can
-int asr_shard_before_conv(asr_hip_context* ctx, asr_shard_state* st, const void* rs, void* feat, i64 ld_bytes, i64 row_bytes,
-                          float* imp, unsigned* in_amax, const int32_t** perm, i64* num_out, const asr_conv_plan** plan) {
-    auto it = st->csr.find(rs);
-    if (it == st->csr.end()) ASR_FAIL(ctx, ASR_HIP_ELOGIC, "sharded forward: convolution over an unknown neighbour list");
-    ShardCsr& c = it->second;
-    *perm = c.perm;
-    *num_out = c.num_out;
-    *plan = c.has_plan ? &c.plan : nullptr;
+int asr_shard_before_conv(asr_hip_context* ctx, asr_shard_state* st, const NbList& list, void* feat, i64 ld_bytes,
+                          i64 row_bytes, float* imp, unsigned* in_amax, const asr_conv_plan** rows) {
+    ShardCsr& c = st->csr[list.id];
+    *rows = &c.rows;
     const i64 ns = c.send_first.back(), nr = c.recv_first.back();
     if (st->world == 1) return ASR_HIP_OK;
     if (ns == 0 && nr == 0) {  // no halo here, but the maximum is a collective: every rank takes part
