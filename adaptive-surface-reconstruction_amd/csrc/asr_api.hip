@@ -648,7 +648,8 @@ int asr_hip_row_groups(asr_hip_context* ctx, const uint8_t* kidx, const int64_t*
     if (v < 0 || (v > 0 && (!kidx || !rs || !perm_out)))
         ASR_FAIL(ctx, ASR_HIP_EINVAL, "row_groups: null argument");
     ctx->scratch.reset();
-    return asr_geom_row_groups(ctx, kidx, rs, v, seg > 0 ? seg : ASR_ROW_GROUP_SEGMENT, perm_out, 56);
+    const asr_row_group_job job = {kidx, rs, v, 56, perm_out};  // a batch of one list, sorted on the whole mask
+    return asr_geom_row_groups_batch(ctx, &job, 1, seg > 0 ? seg : ASR_ROW_GROUP_SEGMENT, 0, false);
 }
 int asr_hip_invert_neighbors_list(asr_hip_context* ctx, int64_t num_points, const int32_t* idx,
                                   const int64_t* rs, int64_t num_rows, const uint8_t* attr,
@@ -1274,7 +1275,9 @@ int build_tilings_and_plans(asr_hip_context* ctx, asr_hip_context* on, int preci
             if ((l.kind == NbList::SAME) == (wide != 0))
                 rg_jobs.push_back({l.kidx, l.rs, l.num_out, l.K, const_cast<int32_t*>(l.perm)});
     on->scratch.reset();
-    if (asr_geom_row_groups_batch(on, rg_jobs.data(), (int)rg_jobs.size(), ASR_ROW_GROUP_SEGMENT) != ASR_HIP_OK) {
+    // (segments of at least one 128-row chunk; the lists of a build order alike with and without slot 0: mask shift 1)
+    if (asr_geom_row_groups_batch(on, rg_jobs.data(), (int)rg_jobs.size(), std::max<i64>(ASR_ROW_GROUP_SEGMENT, 128), 1,
+                                  on->opt.row_ranked != 0) != ASR_HIP_OK) {
         if (on != ctx) ctx->err = on->err;
         return ASR_HIP_EHIP;
     }

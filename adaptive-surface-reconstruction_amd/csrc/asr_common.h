@@ -132,7 +132,7 @@ struct asr_conv_rows {
     const int32_t* nidx = nullptr;
     const uint8_t* kidx = nullptr;
     const i64* rs = nullptr;
-    const int32_t* perm = nullptr;  // tiling order (asr_geom_row_groups): num_out rows of the list, or null
+    const int32_t* perm = nullptr;  // tiling order (asr_geom_row_groups_batch): num_out rows of the list, or null
     i64 num_out = 0;
     int K = 0;
 };
@@ -477,16 +477,17 @@ struct asr_nb_job {
     int me = 0;
 };
 int asr_geom_neighbors_build_batch(asr_hip_context* ctx, Arena& out_arena, asr_nb_job* jobs, int n);
-int asr_geom_row_groups(asr_hip_context* ctx, const uint8_t* kidx, const i64* rs, i64 v, i64 seg,
-                        int32_t* perm_out, int kbits);
 struct asr_row_group_job {
     const uint8_t* kidx;
     const i64* rs;
     i64 v;
-    int kbits;
+    int kbits;  // the list's slots are below this (at most 56)
     int32_t* perm_out;
 };
-int asr_geom_row_groups_batch(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, i64 seg);
+// MFMA tiling order of every list, rows regrouped inside segments of seg >= 16 rows by their slot mask >> mask_shift;
+// ranked: sort on the masks' ranks where that is possible (option "row_ranked")
+int asr_geom_row_groups_batch(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, i64 seg, int mask_shift,
+                              bool ranked);
 int asr_geom_coarsen_count(asr_hip_context* ctx, const u64* keys, i64 v, i64* v_out);
 // EINVAL when v_out is not what asr_geom_coarsen_count gives
 int asr_geom_coarsen_fill(asr_hip_context* ctx, const u64* keys, i64 v, u64* out_keys, i64 v_out,

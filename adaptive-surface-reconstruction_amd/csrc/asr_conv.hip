@@ -1029,7 +1029,7 @@ __global__ void k_sconv_scalar(asr_sparse_conv_args a) {
 // a12 MFMA kernel (v2).
 // Block = 256 threads = 4 waves; tile = 64 output rows (16 per wave) x NCOL = NT*16 output
 // columns (several column chunks per row tile share an XCD, see the block index mapping).  Rows come from an optional permutation that
-// groups rows with equal kernel-slot signatures (asr_geom_row_groups): ~8 of 55 slots are
+// groups rows with equal kernel-slot signatures (asr_geom_row_groups_batch): ~8 of 55 slots are
 // occupied per voxel and without regrouping a 16-row MFMA tile touches ~23 distinct slots.
 // A dense slot table nbr[64][55] is built in LDS from the CSR rows.  The block walks the slots
 // present in ANY of its rows; per slot and KC-deep cin chunk the W[k] panel [KC x NCOL] is staged

@@ -469,7 +469,9 @@ struct NbBatch {
     const int32_t* owner[NB_MAX_JOBS];  // optional row filter (one rank of a sharded cloud builds its own rows)
     int me[NB_MAX_JOBS];
 };
-__device__ inline int nb_job_of(const NbBatch& b, i64 e) {
+// job of entry e of a batch's shared index space (NbBatch, RowGroupBatch, PlanBatch: n jobs, job j from base[j] on)
+template <class Batch>
+__device__ inline int job_of(const Batch& b, i64 e) {
     int j = 0;
     while (j + 1 < b.n && e >= b.base[j + 1]) ++j;
     return j;
@@ -477,7 +479,7 @@ __device__ inline int nb_job_of(const NbBatch& b, i64 e) {
 __global__ void k_map_build_batch(NbBatch b, int* cnt) {
     const i64 e = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     if (e >= b.base[b.n]) return;
-    const int j = nb_job_of(b, e);
+    const int j = job_of(b, e);
     const i64 i = e - b.base[j];
     if (i >= b.v[j]) return;
     u64 slot;
@@ -490,7 +492,7 @@ __global__ void k_map_build_batch(NbBatch b, int* cnt) {
 __global__ void k_neighbors_count_batch(NbBatch b, i64* counts, u64* masks, int32_t* stage_idx, uint8_t* stage_slot) {
     const i64 e = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     if (e >= b.base[b.n]) return;
-    const int j = nb_job_of(b, e);
+    const int j = job_of(b, e);
     const i64 i = e - b.base[j];
     if (i >= b.v[j]) {  // the job's terminator
         counts[e] = 0;
@@ -539,7 +541,7 @@ __global__ void k_neighbors_fill_batch(NbBatch b, const i64* scan, const u64* ma
                                        const uint8_t* stage_slot) {
     const i64 e = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     if (e >= b.base[b.n]) return;
-    const int j = nb_job_of(b, e);
+    const int j = job_of(b, e);
     const i64 i = e - b.base[j];
     const i64 first = scan[b.base[j]];
     i64 o = scan[e] - first;
@@ -2358,56 +2360,15 @@ __global__ void k_invert_fill(const int32_t* sorted_src, i64 p, const i64* rs, i
 // row regrouping for the MFMA sparse conv: rows of one CSR are reordered inside segments of
 // `seg` consecutive rows so that rows with the same set of kernel slots sit in the same 16-row
 // MFMA tile (ascending 55-bit slot mask).  Purely a tiling order: results do not depend on it.
-// ------------------------------------------------------------------------------------------
-__global__ void k_row_masks(const uint8_t* kidx, const i64* rs, i64 v, u64* masks, int32_t* ids) {
-    i64 q = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    if (q >= v) return;
-    u64 m = 0;
-    for (i64 p = rs[q]; p < rs[q + 1]; ++p) m |= u64(1) << (kidx[p] & 63);
-    masks[q] = m;
-    ids[q] = (int32_t)q;
-}
-// Longest-processing-time order of the 128-row chunks inside each segment: a block's cost is the
-// number of slots in the union of its rows' masks (one weight panel walk + barrier per slot), so
-// heavy tiles start first and the tail of a launch is made of light ones.
-__global__ void k_tile_cost(const int32_t* perm, const u64* masks, i64 v, int32_t* cost) {
-    const i64 tile = (blockIdx.x * (i64)blockDim.x + threadIdx.x) >> 6;  // one wave per 64-row tile
-    const int lane = threadIdx.x & 63;
-    if (tile * 64 >= v) return;
-    const i64 r = tile * 64 + lane;
-    u64 m = r < v ? masks[perm[r]] : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m |= __shfl_xor(m, o, 64);
-    if (lane == 0) cost[tile] = __popcll(m);
-}
-__global__ void k_chunk_key(const int32_t* tile_cost, i64 v, i64 seg, int32_t* key, int32_t* ids) {
-    i64 c = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    i64 r0 = c * 128;
-    if (r0 >= v) return;
-    int cost = tile_cost[2 * c] + (r0 + 64 < v ? tile_cost[2 * c + 1] : 0);
-    if (r0 + 128 > v) cost = 0;  // the partial chunk stays last
-    key[c] = (int32_t)((r0 / seg) * 128 + (127 - cost));
-    ids[c] = (int32_t)c;
-}
-__global__ void k_chunk_apply(const int32_t* perm, const int32_t* order, i64 v, int32_t* out) {
-    i64 r = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    if (r >= v) return;
-    i64 src = (i64)order[r >> 7] * 128 + (r & 127);
-    out[r] = perm[src];
-}
-__global__ void k_segment_of(const int32_t* rows, i64 v, i64 seg, int32_t* out) {
-    i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    if (i < v) out[i] = (int32_t)(rows[i] / seg);
-}
-
-// ------------------------------------------------------------------------------------------
-// batched row regrouping: the 13 CSRs of a grid hierarchy (5 neighbour lists, 4 up lists, 4 inverted up lists)
-// in ONE radix sort + one chunk sort instead of 13 x (2..3 sorts) -- on the small levels each rocPRIM sort is
+//
+// One routine for one list and for the 13 CSRs of a grid hierarchy (5 neighbour lists, 4 up lists, 4 inverted up
+// lists): ONE radix sort + one chunk sort instead of 13 x (2..3 sorts) -- on the small levels each rocPRIM sort is
 // a dozen launches of a few microseconds.  Rows of all jobs live in one index space, every job padded to a
-// multiple of 128 rows; key = job (4 bits) | segment (6 bits) | slot mask without bit 0 (54 bits): the stable
-// sort leaves each job's rows contiguous, ordered by (segment, mask, row) exactly like asr_geom_row_groups.
+// multiple of 128 rows; key = job | segment | slot mask (or its rank among the distinct masks), each field as wide
+// as the jobs at hand need: the stable sort leaves each job's rows contiguous, ordered by (segment, mask, row).
+// Padding rows take the all-ones segment, which no real segment uses, and so sort last inside their job.
 // ------------------------------------------------------------------------------------------
-constexpr int RG_MAX_JOBS = 16;
+constexpr int RG_MAX_JOBS = 16;  // what the argument struct holds; more lists run in groups
 struct RowGroupBatch {
     int n;
     i64 base[RG_MAX_JOBS + 1];  // first padded row of each job (multiples of 128); base[n] = total
@@ -2416,37 +2377,46 @@ struct RowGroupBatch {
     const i64* rs[RG_MAX_JOBS];
     int32_t* out[RG_MAX_JOBS];
 };
-__device__ inline int rg_job_of(const RowGroupBatch& b, i64 e) {
-    int j = 0;
-    while (j + 1 < b.n && e >= b.base[j + 1]) ++j;
-    return j;
+// the (job, segment) field of a key; segment < 0: a padding row
+__device__ inline u64 rg_job_segment(int j, i64 segment, int seg_bits) {
+    return ((u64)j << seg_bits) | (segment < 0 ? (u64(1) << seg_bits) - 1 : (u64)segment);
 }
-// key = (job, segment, slot mask without slot 0) in 4 + 6 + mask_bits bits
-__global__ void k_rg_keys(RowGroupBatch b, i64 seg, u64* keys, u64* masks, int32_t* ids, int mask_bits) {
+// Slot mask of every row (0 for padding rows).  For ranked keys (t.keys set) the distinct masks >> shift are gathered in a
+// small hash set: all but the first insertion of a mask are read-only probes.
+__global__ void k_rg_masks(RowGroupBatch b, u64* masks, int32_t* ids, int shift, HashTab t, int* cnt) {
     const i64 e = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     if (e >= b.base[b.n]) return;
-    const int j = rg_job_of(b, e);
+    const int j = job_of(b, e);
     const i64 r = e - b.base[j];
-    u64 m = 0, key;
+    u64 m = 0;
     if (r < b.v[j]) {
         const i64* rs = b.rs[j];
         const uint8_t* kidx = b.kidx[j];
         for (i64 p = rs[r]; p < rs[r + 1]; ++p) m |= u64(1) << (kidx[p] & 63);
-        key = ((u64)j << (6 + mask_bits)) | ((u64)(r / seg) << mask_bits) | ((m >> 1) & ((u64(1) << mask_bits) - 1));
-    } else {
-        key = ((u64)j << (6 + mask_bits)) | (u64(63) << mask_bits) | ((u64(1) << mask_bits) - 1);  // padding: last inside the job
+        if (t.keys && tab_insert_shared(t, (m >> shift) + 1) < 0) cnt[F_OVERFLOW] = 1;
     }
-    keys[e] = key;
     masks[e] = m;
-    ids[e] = (int32_t)e;
+    if (ids) ids[e] = (int32_t)e;  // (ranked keys: k_rg_keys_ranked writes them; beside the probes the store costs 17 us at 10 M points)
 }
-// 128-row chunks of the sorted order: cost = slots in the union of the rows' masks (as k_tile_cost / k_chunk_key)
+// key = (job, segment, slot mask >> shift) in job_bits + seg_bits + mask_bits <= 64 bits
+__global__ void k_rg_keys(RowGroupBatch b, i64 seg, const u64* masks, u64* keys, int seg_bits, int mask_bits, int shift) {
+    const i64 e = blockIdx.x * (i64)blockDim.x + threadIdx.x;
+    if (e >= b.base[b.n]) return;
+    const int j = job_of(b, e);
+    const i64 r = e - b.base[j];
+    const u64 ones = (u64(1) << mask_bits) - 1;
+    keys[e] = r < b.v[j] ? (rg_job_segment(j, r / seg, seg_bits) << mask_bits) | ((masks[e] >> shift) & ones)
+                         : (rg_job_segment(j, -1, seg_bits) << mask_bits) | ones;
+}
+// Longest-processing-time order of the 128-row chunks inside each segment: a chunk's cost is the number of slots in the
+// union of its rows' masks, per 64-row tile (one weight panel walk + barrier per slot), so heavy tiles start first and the
+// tail of a launch is made of light ones.  key = (job, segment of the chunk's position, 127 - cost); one wave per chunk.
 __global__ void k_rg_chunk_keys(RowGroupBatch b, i64 seg, const int32_t* sorted_ids, const u64* masks, int32_t* ckey,
-                                int32_t* cid) {
-    const i64 c = (blockIdx.x * (i64)blockDim.x + threadIdx.x) >> 6;  // one wave per chunk
+                                int32_t* cid, int seg_bits) {
+    const i64 c = (blockIdx.x * (i64)blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (c * 128 >= b.base[b.n]) return;
-    const int j = rg_job_of(b, c * 128);
+    const int j = job_of(b, c * 128);
     const i64 r0 = c * 128 - b.base[j];
     u64 m0 = masks[sorted_ids[c * 128 + lane]], m1 = masks[sorted_ids[c * 128 + 64 + lane]];
 #pragma unroll
@@ -2455,16 +2425,16 @@ __global__ void k_rg_chunk_keys(RowGroupBatch b, i64 seg, const int32_t* sorted_
         m1 |= __shfl_xor(m1, o, 64);
     }
     if (lane == 0) {
-        int cost = __popcll(m0) + __popcll(m1);  // the two 64-row tiles of the chunk, like k_chunk_key
+        int cost = __popcll(m0) + __popcll(m1);  // the two 64-row tiles of the chunk
         if (r0 + 128 > b.v[j]) cost = 0;         // the partial chunk stays last
-        ckey[c] = (int32_t)(((i64)j << 13) | ((r0 / seg) << 7) | (127 - cost));
+        ckey[c] = (int32_t)((rg_job_segment(j, r0 / seg, seg_bits) << 7) | (u64)(127 - cost));
         cid[c] = (int32_t)c;
     }
 }
 __global__ void k_rg_apply(RowGroupBatch b, const int32_t* sorted_ids, const int32_t* order, int lpt) {
     const i64 e = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     if (e >= b.base[b.n]) return;
-    const int j = rg_job_of(b, e);
+    const int j = job_of(b, e);
     const i64 r = e - b.base[j];
     if (r >= b.v[j]) return;
     const i64 src = lpt ? (i64)order[e >> 7] * 128 + (e & 127) : e;
@@ -2472,27 +2442,13 @@ __global__ void k_rg_apply(RowGroupBatch b, const int32_t* sorted_ids, const int
 }
 
 // Ranked keys (round 4): a hierarchy has a few thousand DISTINCT slot masks, so the 54 mask bits of the sort key are replaced
-// by the mask's rank among the distinct masks (same order, same permutation): (job, segment, rank) is 22 bits -- three digit
-// passes over all 13 lists in one sort instead of three passes over the 9-slot lists plus eight over the 55-slot ones.
-// Distinct masks: a small hash set (k_rg_masks: all but the first insertion of a mask are read-only probes), collected into a
-// dense list (k_rg_mask_collect) and ranked by counting (k_rg_mask_ranks), rank written back as the set's value.  More than
-// RG_MAX_MASKS distinct masks: the caller falls back to the full-mask keys.
+// by the mask's rank among the distinct masks (same order, same permutation): (job, segment, rank) is at most 22 bits -- three
+// digit passes over all 13 lists in one sort instead of three passes over the 9-slot lists plus eight over the 55-slot ones.
+// Distinct masks: the hash set k_rg_masks filled, collected into a dense list (k_rg_mask_collect) and ranked by counting
+// (k_rg_mask_ranks), rank written back as the set's value.  More than RG_MAX_MASKS distinct masks, or a key of more than
+// 32 bits: the caller falls back to the full-mask keys.
 constexpr int RG_MAX_MASKS = 16384;  // (C3: ~1 500 distinct masks, mixed-density C5: more than 4 096)
 constexpr int RG_MASK_TAB = 65536;
-__global__ void k_rg_masks(RowGroupBatch b, u64* masks, HashTab t, int* cnt) {
-    const i64 e = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    if (e >= b.base[b.n]) return;
-    const int j = rg_job_of(b, e);
-    const i64 r = e - b.base[j];
-    u64 m = 0;
-    if (r < b.v[j]) {
-        const i64* rs = b.rs[j];
-        const uint8_t* kidx = b.kidx[j];
-        for (i64 p = rs[r]; p < rs[r + 1]; ++p) m |= u64(1) << (kidx[p] & 63);
-        if (tab_insert_shared(t, (m >> 1) + 1) < 0) cnt[F_OVERFLOW] = 1;
-    }
-    masks[e] = m;
-}
 // the set's keys as a dense list (any order) with their slots; cnt[F_MASKS] = how many
 __global__ void k_rg_mask_collect(HashTab t, u64* list, int32_t* slot_of, int* cnt) {
     const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
@@ -2523,22 +2479,18 @@ __global__ __launch_bounds__(256) void k_rg_mask_ranks(HashTab t, const u64* lis
     }
     if (i < n) t.vals[slot_of[i]] = rank;
 }
-// key = (job, segment, rank of the slot mask) in 4 + 6 + rank_bits bits
-__global__ void k_rg_keys_ranked(RowGroupBatch b, i64 seg, const u64* masks, HashTab t, unsigned* keys, int32_t* ids,
-                                 int rank_bits) {
-    const i64 e = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    if (e >= b.base[b.n]) return;
-    const int j = rg_job_of(b, e);
+// key = (job, segment, rank of the slot mask >> shift) in job_bits + seg_bits + rank_bits <= 32 bits, of row order[i] (of row
+// i without an order).  rank_bits = 0 leaves (job, segment): the second of two stable sorts, over rows already in mask order.
+__global__ void k_rg_keys_ranked(RowGroupBatch b, i64 seg, const u64* masks, const int32_t* order, HashTab t, unsigned* keys,
+                                 int32_t* ids, int seg_bits, int rank_bits, int shift) {
+    const i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x;
+    if (i >= b.base[b.n]) return;
+    const i64 e = order ? order[i] : i;
+    if (!order) ids[i] = (int32_t)i;
+    const int j = job_of(b, e);
     const i64 r = e - b.base[j];
-    unsigned key;
-    if (r < b.v[j]) {
-        const int rank = tab_find(t, (masks[e] >> 1) + 1);
-        key = ((unsigned)j << (6 + rank_bits)) | ((unsigned)(r / seg) << rank_bits) | (unsigned)rank;
-    } else {
-        key = ((unsigned)j << (6 + rank_bits)) | (63u << rank_bits) | ((1u << rank_bits) - 1u);  // padding: last inside the job
-    }
-    keys[e] = key;
-    ids[e] = (int32_t)e;
+    const u64 low = r >= b.v[j] ? (u64(1) << rank_bits) - 1 : rank_bits ? (u64)tab_find(t, (masks[e] >> shift) + 1) : 0;
+    keys[i] = (unsigned)((rg_job_segment(j, r < b.v[j] ? r / seg : -1, seg_bits) << rank_bits) | low);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2987,106 +2939,11 @@ int asr_geom_neighbors_build_batch(asr_hip_context* ctx, Arena& out_arena, asr_n
     return ASR_HIP_OK;
 }
 
-int asr_geom_row_groups(asr_hip_context* ctx, const uint8_t* kidx, const i64* rs, i64 v, i64 seg,
-                        int32_t* perm_out, int kbits) {
-    if (kbits < 1 || kbits > 56) kbits = 56;  // slot masks only use bits below the kernel size
-    if (v <= 0) return ASR_HIP_OK;
-    if (seg < 16) seg = 16;
-    if (v >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "row_groups: too many rows");
-    u64* masks = arena_alloc<u64>(ctx->scratch, v);
-    u64* masks_s = arena_alloc<u64>(ctx->scratch, v);
-    int32_t* ids = arena_alloc<int32_t>(ctx->scratch, v);
-    if (!masks || !masks_s || !ids) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-    k_row_masks<<<grid_for(v, BLK), BLK, 0, ctx->stream>>>(kidx, rs, v, masks, ids);
-    ASR_CHECK_LAUNCH(ctx);
-    // order by (segment, mask) with two stable LSD radix sorts: by mask, then by segment id
-    const bool lpt = ctx->opt.row_lpt != 0;
-    int32_t* perm_m = perm_out;  // (segment, mask) order; re-ordered by chunk cost below
-    if (lpt && v > 128) {
-        perm_m = arena_alloc<int32_t>(ctx->scratch, v);
-        if (!perm_m) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-    }
-    if (seg >= v) {
-        ASR_TRY((sort_pairs<u64, int32_t>(ctx, ctx->scratch, masks, masks_s, ids, perm_m, v, kbits)));
-    } else {
-        int32_t* ids_m = arena_alloc<int32_t>(ctx->scratch, v);
-        int32_t* segk = arena_alloc<int32_t>(ctx->scratch, v);
-        int32_t* segk_s = arena_alloc<int32_t>(ctx->scratch, v);
-        if (!ids_m || !segk || !segk_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-        ASR_TRY((sort_pairs<u64, int32_t>(ctx, ctx->scratch, masks, masks_s, ids, ids_m, v, kbits)));
-        k_segment_of<<<grid_for(v, BLK), BLK, 0, ctx->stream>>>(ids_m, v, seg, segk);
-        ASR_CHECK_LAUNCH(ctx);
-        ASR_TRY((sort_pairs<int32_t, int32_t>(ctx, ctx->scratch, segk, segk_s, ids_m, perm_m, v,
-                                              bits_for((v + seg - 1) / seg + 1))));
-    }
-    if (perm_m != perm_out) {
-        const i64 nc = (v + 127) / 128;
-        int32_t* ckey = arena_alloc<int32_t>(ctx->scratch, nc);
-        int32_t* ckey_s = arena_alloc<int32_t>(ctx->scratch, nc);
-        int32_t* cid = arena_alloc<int32_t>(ctx->scratch, nc);
-        int32_t* cid_s = arena_alloc<int32_t>(ctx->scratch, nc);
-        if (!ckey || !ckey_s || !cid || !cid_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-        int32_t* tcost = arena_alloc<int32_t>(ctx->scratch, 2 * nc);
-        if (!tcost) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-        k_tile_cost<<<grid_for(((v + 63) / 64) * 64, BLK), BLK, 0, ctx->stream>>>(perm_m, masks, v, tcost);
-        ASR_CHECK_LAUNCH(ctx);
-        k_chunk_key<<<grid_for(nc, BLK), BLK, 0, ctx->stream>>>(tcost, v, seg, ckey, cid);
-        ASR_CHECK_LAUNCH(ctx);
-        ASR_TRY((sort_pairs<int32_t, int32_t>(ctx, ctx->scratch, ckey, ckey_s, cid, cid_s, nc,
-                                              7 + bits_for((v + seg - 1) / seg + 1))));
-        k_chunk_apply<<<grid_for(v, BLK), BLK, 0, ctx->stream>>>(perm_m, cid_s, v, perm_out);
-        ASR_CHECK_LAUNCH(ctx);
-    }
-    return ASR_HIP_OK;
-}
-
-// all CSRs of one hierarchy in one pass (see k_rg_keys); falls back to the per-CSR routine for shapes the
-// packed key cannot hold
-static int rg_batch_run(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, i64 seg, int mask_bits);
-static int rg_batch_run_ranked(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, i64 seg, bool* done);
-int asr_geom_row_groups_batch(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, i64 seg) {
-    if (seg < 128) seg = 128;
-    bool fits = n <= RG_MAX_JOBS && seg % 128 == 0;
-    for (int j = 0; j < n && fits; ++j) fits = jobs[j].v / seg < 63 && jobs[j].v < (i64(1) << 31);
-    if (!fits) {
-        for (int j = 0; j < n; ++j)
-            ASR_TRY(asr_geom_row_groups(ctx, jobs[j].kidx, jobs[j].rs, jobs[j].v, seg, jobs[j].perm_out, jobs[j].kbits));
-        return ASR_HIP_OK;
-    }
-    // The radix sort of the keys is what this routine costs.  Lists with few slots (the 9-slot up / down lists: more than
-    // half of all rows of a hierarchy) go through it with 19-bit keys, three digit passes instead of eight.
-    if (ctx->opt.row_ranked) {  // all lists in one sort on (job, segment, rank of the mask) keys
-        bool done = false;
-        ASR_TRY(rg_batch_run_ranked(ctx, jobs, n, seg, &done));
-        if (done) return ASR_HIP_OK;
-    }
-    std::vector<asr_row_group_job> small_jobs, wide_jobs;
-    for (int j = 0; j < n; ++j) (jobs[j].kbits <= 10 ? small_jobs : wide_jobs).push_back(jobs[j]);
-    if (!small_jobs.empty()) ASR_TRY(rg_batch_run(ctx, small_jobs.data(), (int)small_jobs.size(), seg, 9));
-    if (!wide_jobs.empty()) ASR_TRY(rg_batch_run(ctx, wide_jobs.data(), (int)wide_jobs.size(), seg, 54));
-    return ASR_HIP_OK;
-}
-// the jobs that have rows, each padded to a multiple of 128 rows, in one index space; *total = its size (0: nothing to do)
-static int rg_pack(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, RowGroupBatch& b, i64* total) {
-    b.n = 0;
-    *total = 0;
-    for (int j = 0; j < n; ++j) {
-        if (jobs[j].v <= 0) continue;
-        b.base[b.n] = *total;
-        b.v[b.n] = jobs[j].v;
-        b.kidx[b.n] = jobs[j].kidx;
-        b.rs[b.n] = jobs[j].rs;
-        b.out[b.n] = jobs[j].perm_out;
-        *total += (jobs[j].v + 127) / 128 * 128;
-        ++b.n;
-    }
-    b.base[b.n] = *total;
-    if (*total >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "row_groups: too many rows");
-    return ASR_HIP_OK;
-}
-// what both key types end with: ids_s = the rows in (job, segment, mask) order, masks = slot mask per row.  Option row_lpt:
-// the 128-row chunks of every segment longest first (k_rg_chunk_keys); then each job's permutation is written.
-static int rg_finish(asr_hip_context* ctx, const RowGroupBatch& b, i64 total, i64 seg, const int32_t* ids_s, const u64* masks) {
+// what every key type ends with: ids_s = the rows in (job, segment, mask) order, masks = slot mask per row.  Option row_lpt:
+// the 128-row chunks of every segment longest first (k_rg_chunk_keys; a list of one chunk keeps its order); then each
+// job's permutation is written.
+static int rg_finish(asr_hip_context* ctx, const RowGroupBatch& b, i64 total, i64 seg, int job_bits, int seg_bits,
+                     const int32_t* ids_s, const u64* masks) {
     const i64 nc = total / 128;
     int32_t* ckey = arena_alloc<int32_t>(ctx->scratch, nc);
     int32_t* ckey_s = arena_alloc<int32_t>(ctx->scratch, nc);
@@ -3095,69 +2952,110 @@ static int rg_finish(asr_hip_context* ctx, const RowGroupBatch& b, i64 total, i6
     if (!ckey || !ckey_s || !cid || !cid_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
     const int lpt = ctx->opt.row_lpt != 0;
     if (lpt) {
-        k_rg_chunk_keys<<<grid_for(nc * 64, BLK), BLK, 0, ctx->stream>>>(b, seg, ids_s, masks, ckey, cid);
+        if (job_bits + seg_bits + 7 > 31) ASR_FAIL(ctx, ASR_HIP_EINVAL, "row_groups: too many segments");
+        k_rg_chunk_keys<<<grid_for(nc * 64, BLK), BLK, 0, ctx->stream>>>(b, seg, ids_s, masks, ckey, cid, seg_bits);
         ASR_CHECK_LAUNCH(ctx);
-        ASR_TRY((sort_pairs<int32_t, int32_t>(ctx, ctx->scratch, ckey, ckey_s, cid, cid_s, nc, 17)));
+        ASR_TRY((sort_pairs<int32_t, int32_t>(ctx, ctx->scratch, ckey, ckey_s, cid, cid_s, nc, job_bits + seg_bits + 7)));
     }
     k_rg_apply<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, ids_s, cid_s, lpt);
     ASR_CHECK_LAUNCH(ctx);
     return ASR_HIP_OK;
 }
-// *done = false: more than RG_MAX_MASKS distinct masks (or a full mask set): nothing written, the caller sorts on full masks
-static int rg_batch_run_ranked(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, i64 seg, bool* done) {
-    *done = false;
-    ASR_TRY(ensure_flags(ctx));
+// The tiling orders of up to RG_MAX_JOBS lists: pack, masks, keys, sort, finish.  `ranked` set: keys on the rank of the mask;
+// *ranked = false on return: they cannot be used (more than RG_MAX_MASKS distinct masks, a full mask set, a key of more than
+// 32 bits), nothing is written and the caller sorts on full masks.  `ranked` null: keys on the mask itself, in one sort if
+// job + segment + mask fit 64 bits, else by mask and then, stably, by (job, segment) with the ranked kernel and no rank.
+static int rg_run(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, i64 seg, int shift, bool* ranked) {
     RowGroupBatch b;
-    i64 total;
-    ASR_TRY(rg_pack(ctx, jobs, n, b, &total));
-    if (b.n == 0) {
-        *done = true;
-        return ASR_HIP_OK;
+    b.n = 0;
+    i64 total = 0, segments = 1;
+    int kbits = 1;  // slot masks only use bits below the kernel size
+    for (int j = 0; j < n; ++j) {
+        if (jobs[j].v <= 0) continue;
+        b.base[b.n] = total;
+        b.v[b.n] = jobs[j].v;
+        b.kidx[b.n] = jobs[j].kidx;
+        b.rs[b.n] = jobs[j].rs;
+        b.out[b.n] = jobs[j].perm_out;
+        total += (jobs[j].v + 127) / 128 * 128;
+        segments = std::max(segments, (jobs[j].v + seg - 1) / seg);
+        kbits = std::max(kbits, jobs[j].kbits >= 1 && jobs[j].kbits <= 56 ? jobs[j].kbits : 56);
+        ++b.n;
     }
+    b.base[b.n] = total;
+    if (b.n == 0) return ASR_HIP_OK;
+    if (total >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "row_groups: too many rows");
+    const int job_bits = b.n > 1 ? bits_for(b.n) : 0, seg_bits = bits_for(segments + 1), mask_bits = kbits - shift;
     u64* masks = arena_alloc<u64>(ctx->scratch, total);
+    int32_t* ids = arena_alloc<int32_t>(ctx->scratch, total);
+    int32_t* ids_s = arena_alloc<int32_t>(ctx->scratch, total);
+    if (!masks || !ids || !ids_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    HashTab t{};
+    if (ranked) {
+        ASR_TRY(ensure_flags(ctx));
+        ASR_TRY(make_table(ctx, ctx->scratch, RG_MASK_TAB, true, t));
+        ASR_TRY(fresh_flags(ctx));
+    }
+    k_rg_masks<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, masks, ranked ? nullptr : ids, shift, t, ctx->d_flags);
+    ASR_CHECK_LAUNCH(ctx);
+    int low_bits = 0;  // of a 32-bit key below (job, segment): the rank of the mask, or nothing
+    if (ranked) {
+        u64* mlist = arena_alloc<u64>(ctx->scratch, RG_MAX_MASKS);
+        int32_t* mslot = arena_alloc<int32_t>(ctx->scratch, RG_MAX_MASKS);
+        if (!mlist || !mslot) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+        k_rg_mask_collect<<<grid_for((i64)t.mask + 1, BLK), BLK, 0, ctx->stream>>>(t, mlist, mslot, ctx->d_flags);
+        ASR_CHECK_LAUNCH(ctx);
+        k_rg_mask_ranks<<<RG_MAX_MASKS / 256, 256, 0, ctx->stream>>>(t, mlist, mslot, ctx->d_flags);
+        ASR_CHECK_LAUNCH(ctx);
+        HostFlags host;
+        ASR_TRY(read_flags(ctx, host));
+        low_bits = bits_for(std::max(host[F_MASKS], 2));
+        if (host[F_OVERFLOW] || host[F_MASKS] > RG_MAX_MASKS || job_bits + seg_bits + low_bits > 32) {
+            *ranked = false;
+            return ASR_HIP_OK;
+        }
+    } else if (job_bits + seg_bits + mask_bits <= 64) {
+        u64* keys = arena_alloc<u64>(ctx->scratch, total);
+        u64* keys_s = arena_alloc<u64>(ctx->scratch, total);
+        if (!keys || !keys_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+        k_rg_keys<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, seg, masks, keys, seg_bits, mask_bits, shift);
+        ASR_CHECK_LAUNCH(ctx);
+        ASR_TRY((sort_pairs<u64, int32_t>(ctx, ctx->scratch, keys, keys_s, ids, ids_s, total, job_bits + seg_bits + mask_bits)));
+        return rg_finish(ctx, b, total, seg, job_bits, seg_bits, ids_s, masks);
+    } else {  // by mask first (the masks are their own keys), which leaves (job, segment): at most 4 + 28 bits
+        u64* masks_s = arena_alloc<u64>(ctx->scratch, total);
+        int32_t* ids_m = arena_alloc<int32_t>(ctx->scratch, total);
+        if (!masks_s || !ids_m) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+        ASR_TRY((sort_pairs<u64, int32_t>(ctx, ctx->scratch, masks, masks_s, ids, ids_m, total, shift + mask_bits, shift)));
+        ids = ids_m;
+    }
     unsigned* keys = arena_alloc<unsigned>(ctx->scratch, total);
     unsigned* keys_s = arena_alloc<unsigned>(ctx->scratch, total);
-    int32_t* ids = arena_alloc<int32_t>(ctx->scratch, total);
-    int32_t* ids_s = arena_alloc<int32_t>(ctx->scratch, total);
-    if (!masks || !keys || !keys_s || !ids || !ids_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-    HashTab t;
-    ASR_TRY(make_table(ctx, ctx->scratch, RG_MASK_TAB, true, t));
-    ASR_TRY(fresh_flags(ctx));
-    k_rg_masks<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, masks, t, ctx->d_flags);
+    if (!keys || !keys_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
+    k_rg_keys_ranked<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, seg, masks, ranked ? nullptr : ids, t, keys, ids,
+                                                                    seg_bits, low_bits, shift);
     ASR_CHECK_LAUNCH(ctx);
-    u64* mlist = arena_alloc<u64>(ctx->scratch, RG_MAX_MASKS);
-    int32_t* mslot = arena_alloc<int32_t>(ctx->scratch, RG_MAX_MASKS);
-    if (!mlist || !mslot) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-    k_rg_mask_collect<<<grid_for((i64)t.mask + 1, BLK), BLK, 0, ctx->stream>>>(t, mlist, mslot, ctx->d_flags);
-    ASR_CHECK_LAUNCH(ctx);
-    k_rg_mask_ranks<<<RG_MAX_MASKS / 256, 256, 0, ctx->stream>>>(t, mlist, mslot, ctx->d_flags);
-    ASR_CHECK_LAUNCH(ctx);
-    HostFlags host;
-    ASR_TRY(read_flags(ctx, host));
-    if (host[F_OVERFLOW] || host[F_MASKS] > RG_MAX_MASKS) return ASR_HIP_OK;  // too many distinct masks for the ranked keys
-    const int rank_bits = bits_for(std::max(host[F_MASKS], 2));
-    k_rg_keys_ranked<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, seg, masks, t, keys, ids, rank_bits);
-    ASR_CHECK_LAUNCH(ctx);
-    ASR_TRY((sort_pairs<unsigned, int32_t>(ctx, ctx->scratch, keys, keys_s, ids, ids_s, total, 4 + 6 + rank_bits)));
-    ASR_TRY(rg_finish(ctx, b, total, seg, ids_s, masks));
-    *done = true;
-    return ASR_HIP_OK;
+    ASR_TRY((sort_pairs<unsigned, int32_t>(ctx, ctx->scratch, keys, keys_s, ids, ids_s, total, job_bits + seg_bits + low_bits)));
+    return rg_finish(ctx, b, total, seg, job_bits, seg_bits, ids_s, masks);
 }
-static int rg_batch_run(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, i64 seg, int mask_bits) {
-    RowGroupBatch b;
-    i64 total;
-    ASR_TRY(rg_pack(ctx, jobs, n, b, &total));
-    if (b.n == 0) return ASR_HIP_OK;
-    u64* keys = arena_alloc<u64>(ctx->scratch, total);
-    u64* keys_s = arena_alloc<u64>(ctx->scratch, total);
-    u64* masks = arena_alloc<u64>(ctx->scratch, total);
-    int32_t* ids = arena_alloc<int32_t>(ctx->scratch, total);
-    int32_t* ids_s = arena_alloc<int32_t>(ctx->scratch, total);
-    if (!keys || !keys_s || !masks || !ids || !ids_s) ASR_FAIL(ctx, ASR_HIP_EHIP, "arena allocation failed");
-    k_rg_keys<<<grid_for(total, BLK), BLK, 0, ctx->stream>>>(b, seg, keys, masks, ids, mask_bits);
-    ASR_CHECK_LAUNCH(ctx);
-    ASR_TRY((sort_pairs<u64, int32_t>(ctx, ctx->scratch, keys, keys_s, ids, ids_s, total, 4 + 6 + mask_bits)));
-    return rg_finish(ctx, b, total, seg, ids_s, masks);
+// lists with fewer than 16 rows per segment make no tile; more lists than one batch holds run in groups (no hierarchy has them)
+int asr_geom_row_groups_batch(asr_hip_context* ctx, const asr_row_group_job* jobs, int n, i64 seg, int mask_shift, bool ranked) {
+    if (seg < 16) seg = 16;
+    for (; n > 0; jobs += RG_MAX_JOBS, n -= RG_MAX_JOBS) {
+        const int g = std::min(n, RG_MAX_JOBS);
+        if (ranked) {  // all lists in one sort on (job, segment, rank of the mask) keys
+            bool done = true;
+            ASR_TRY(rg_run(ctx, jobs, g, seg, mask_shift, &done));
+            if (done) continue;
+        }
+        // The radix sort of the keys is what this routine costs.  Lists with few slots (the 9-slot up / down lists: more than
+        // half of all rows of a hierarchy) go through it with short keys, three digit passes instead of eight.
+        std::vector<asr_row_group_job> small_jobs, wide_jobs;
+        for (int j = 0; j < g; ++j) (jobs[j].kbits <= 10 ? small_jobs : wide_jobs).push_back(jobs[j]);
+        ASR_TRY(rg_run(ctx, small_jobs.data(), (int)small_jobs.size(), seg, mask_shift, nullptr));
+        ASR_TRY(rg_run(ctx, wide_jobs.data(), (int)wide_jobs.size(), seg, mask_shift, nullptr));
+    }
+    return ASR_HIP_OK;
 }
 
 // CombineSiblings in two steps (k_coarsen_flags above); the keys are sorted and unique, as those of every grid.
@@ -4209,15 +4107,10 @@ struct PlanBatch {
     const i64* rs[PLAN_MAX_JOBS];
     const int32_t* perm[PLAN_MAX_JOBS];
 };
-__device__ inline int plan_job_of(const PlanBatch& b, i64 row) {
-    int j = 0;
-    while (j + 1 < b.n && row >= b.base[j + 1]) ++j;
-    return j;
-}
 __global__ void k_plan_masks_batch(PlanBatch b, uint4* __restrict__ hdr, i64* __restrict__ counts) {
     const i64 grow = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     if (grow >= b.base[b.n]) return;
-    const int j = plan_job_of(b, grow);
+    const int j = job_of(b, grow);
     const i64 row = grow - b.base[j];
     unsigned long long m = 0;
     if (row < b.rows[j]) {
@@ -4245,7 +4138,7 @@ __global__ void k_plan_fill_batch(PlanBatch b, const i64* __restrict__ offs, uin
     const i64 grp = grow >> 4;
     const unsigned off = (unsigned)offs[grp];
     if ((grow & 15) == 0) hdr[grp].z = off;
-    const int j = plan_job_of(b, grow);
+    const int j = job_of(b, grow);
     const i64 row = grow - b.base[j];
     const uint2 h = *reinterpret_cast<const uint2*>(&hdr[grp]);
     unsigned long long m = (unsigned long long)h.x | ((unsigned long long)h.y << 32);

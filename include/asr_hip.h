@@ -437,7 +437,10 @@ int asr_hip_convert_f16(asr_hip_context* ctx, const void* in_dev, int64_t n, voi
  * row (an empty row: 0); then, with option row_lpt and more than 128 rows, the 128-row chunks of that order
  * stably by (128 c / segment_rows) * 128 + 127 - cost, cost = slots in the union of the chunk's first 64 rows
  * + the same for its second 64 rows, 0 for the partial last chunk.  Always a permutation; for segment_rows a
- * multiple of 128 every row stays inside its segment (tests/list_ops_ref.py). */
+ * multiple of 128 every row stays inside its segment (tests/list_ops_ref.py).
+ * The list goes through the routine that orders the 13 lists of a build, as a batch of one list sorted on the whole
+ * mask, whatever option row_ranked says: any segment_rows (below 16: 16) and any num_rows below 2^31 - 127; with
+ * row_lpt, EINVAL for 2^24 segments and more (the chunk key is 31 bits). */
 int asr_hip_row_groups(asr_hip_context* ctx, const uint8_t* kernel_index_dev,
                        const int64_t* row_splits_dev, int64_t num_rows, int64_t segment_rows,
                        int32_t* perm_out_dev);

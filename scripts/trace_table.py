@@ -29,7 +29,7 @@ for n, (c, d) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:top]:
     print("%9.1f us %5d  %s" % (d, c, n))
 
 # spans: wall time from each occurrence of kernel A to the end of the next occurrence of kernel B
-SPANS = [("row_groups", "k_row_masks", "k_chunk_apply"), ("coarsen", "k_coarsen_flags", "k_coarsen_up"),
+SPANS = [("row_groups", "k_rg_masks", "k_rg_apply"), ("coarsen", "k_coarsen_flags", "k_coarsen_up"),
          ("invert", "k_invert_hist", "k_invert_fill"), ("neighbors", "k_map_build_batch", "k_neighbors_fill_batch"),
          ("octree", "k_octree_insert_points", "k_collect_leaves"), ("search", "k_query_levels", "k_radius_place")]
 names = [r["Kernel_Name"] for r in last]

@@ -1,5 +1,5 @@
 """Synthetic lists and plain NumPy restatements for the small operators between the convolutions: row regrouping
-(asr_geom_row_groups / asr_geom_row_groups_batch), invert_neighbors_list, reduce_subarrays_sum, decode_mlp, and the f16
+(asr_geom_row_groups_batch), invert_neighbors_list, reduce_subarrays_sum, decode_mlp, and the f16
 conversion behind asr_hip_convert_f16.
 
 The lists of an octree build all look alike: rows of 4 to 25 entries, never an empty row, slot 0 in every neighbour row,
@@ -15,7 +15,9 @@ import sconv_lists as L
 from sconv_lists import row_of_pairs
 
 DEFAULT_SEGMENT = 524288  # option "row_segment"; what segment_rows = 0 means
-ROW_GROUP_ROWS = L.TILE_EDGE_ROWS + (255, 256, 257, 1000, 3001)
+# 3001 rows in 16-row segments: 188 segments, an 8-bit segment field + the 56-bit mask = one 64-bit key; 4200 rows: 263
+# segments, 9 + 56 bits, which takes two sorts (by mask, then by segment)
+ROW_GROUP_ROWS = L.TILE_EDGE_ROWS + (255, 256, 257, 1000, 3001, 4200)
 SEGMENT_ROWS = (0, 16, 100, 128, 256, 1024)
 POOL_SIZES = (1, 5, 40)
 POOL_KERNEL_SIZES = (9, 27, 55)

@@ -1,5 +1,5 @@
 """The small operators between the convolutions, each alone and on lists an octree build never produces: row regrouping
-(asr_geom_row_groups, asr_geom_row_groups_batch with its ranked-key and full-mask-key routines and its fallback),
+(asr_geom_row_groups_batch: one list or the 13 of a build, ranked keys or full-mask keys, one sort or two),
 invert_neighbors_list, reduce_subarrays_sum, decode_mlp (k_decode_mfma, the generic k_decode, the unaligned fallback),
 asr_hip_absmax_f32 and asr_hip_convert_f16 -- against the plain NumPy restatements of tests/list_ops_ref.py, which
 tests/test_list_ops.py pins on the CPU.  Integer results bit for bit; sums and the decoder within the bounds stated at
@@ -42,7 +42,9 @@ def _check_order(perm, lst, seg, lpt, drop_slot0, what):
 @pytest.mark.parametrize("v", R.ROW_GROUP_ROWS)
 def test_row_groups_of_one_list_follow_the_documented_order(gpu, v, lpt):
     """asr_hip_row_groups on synthetic lists: bit-equal to the restated order (segment, slot mask, row; then the chunks
-    of a segment heaviest first), a permutation, and every row inside its own segment"""
+    of a segment heaviest first), a permutation, and every row inside its own segment.  A batch of one list with full-mask
+    keys: one sort while segment field + 56 mask bits fit 64 bits (up to v = 3001 at 16-row segments, exactly 64), a sort
+    by mask and one by segment beyond (v = 4200 at 16-row segments)"""
     from asr_hip import ops
     ctx = ops.context(gpu)
     lists = R.row_group_lists(v) + (R.fixed_row_group_lists() if v == 200 else ())
@@ -75,8 +77,9 @@ TILINGS = [("tiling%d" % i, "neighbors", i) for i in range(5)] + \
 @pytest.mark.parametrize("lpt", [1, 0])
 @pytest.mark.parametrize("ranked", [1, 0])
 def test_tilings_of_a_build_follow_the_documented_order(gpu, build_cloud, ranked, lpt, seg):
-    """the 13 tilings of implicit_build under every (row_ranked, row_lpt, row_segment): the ranked-key sort, the
-    full-mask-key sorts and, at 128-row segments, the fallback to the per-list routine all give the restated order"""
+    """the 13 tilings of implicit_build under every (row_ranked, row_lpt, row_segment): the ranked-key sort and the
+    full-mask-key sorts give the restated order, at 128-row segments too: the batch has no fallback to another routine, so
+    with row_ranked = 1 the ranked keys serve that build as well, with a segment field of more than 6 bits"""
     pipe, p, rad, bb = build_cloud
     assert len(TILINGS) == 13
     try:
@@ -97,9 +100,9 @@ def test_tilings_of_a_build_follow_the_documented_order(gpu, build_cloud, ranked
         for k, val in (("row_ranked", 1), ("row_lpt", 1), ("row_segment", 524288)):
             pipe.ctx.set_option(k, val)
     if seg == 128:
-        assert rows["tiling0"] >= 63 * 128, rows  # rows // seg >= 63: asr_geom_row_groups_batch takes its fallback
+        assert rows["tiling0"] >= 63 * 128, rows  # rows // seg >= 63: a segment field wider than 6 bits was used
     else:
-        assert all(v // seg < 63 for v in rows.values()), rows  # the batched routines run
+        assert all(v // seg < 63 for v in rows.values()), rows  # the segments fit the 6 bits the field once had: narrow fields
 
 
 # ---- B. invert_neighbors_list ----------------------------------------------------------------------------------------
