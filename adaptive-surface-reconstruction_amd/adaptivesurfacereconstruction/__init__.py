@@ -514,6 +514,125 @@ def register_points(source, target, target_normals=None, init=None, max_distance
     return report
 
 
+def _global_cloud(points, normals, cell_size, feature_k, dev):
+    """steps 1 and 2 of register_points_global and the lists of step 3 for one cloud -> dict: 'points', 'normals' (numpy,
+    the merged cloud), 'pd' (the points on the GPU), 'index' (their feature_k nearest neighbours), 'cell' (the cell used),
+    'estimated' (the normals were not given)"""
+    merged = merge_points(points, normals, cell_size=cell_size)
+    p, n = merged["points"], merged["normals"]
+    if len(p) < 3:
+        raise ValueError("fewer than 3 points are left after the merge: voxel_size is too large")
+    if n is None:
+        est = estimate_normals(p, k=16)
+        p, n = p[est["ok"]], est["normals"][est["ok"]]
+        if len(p) < 3:
+            raise ValueError("fewer than 3 points have a usable normal estimate")
+    pd = torch.from_numpy(p).to(dev)
+    index, _ = _ops.knn_index(_margin_frame(p), pd, feature_k)
+    return {"points": p, "normals": n, "pd": pd, "index": index, "cell": merged["cell_size"], "estimated": normals is None}
+
+
+def _global_descriptors(cloud, dev, flip=False):
+    """step 3 -> (the points that have a descriptor f32 [P,3], their FPFH rows as a GPU tensor [P,33]); flip: with the
+    cloud's normals negated"""
+    normals = torch.from_numpy(-cloud["normals"] if flip else cloud["normals"]).to(dev)
+    fpfh, ok = _ops.point_fpfh(cloud["pd"], normals, cloud["index"], return_ok=True)
+    return cloud["points"][ok.cpu().numpy()], fpfh[ok].contiguous()
+
+
+def _global_pose(sp, sf, tp, tf, mutual, max_distance, hypotheses, seed, dev):
+    """steps 4 and 5 -> (transform f64 [3,4] or None, the report of ransac_transform plus 'correspondences' and
+    'mutual_used')"""
+    if len(sp) < 3 or len(tp) < 3:
+        raise ValueError("fewer than 3 points of a cloud have a descriptor")
+    forth = _ops.feature_match(sf, tf)[0].cpu().numpy()
+    rows = np.nonzero(forth >= 0)[0]
+    corr = np.stack([rows, forth[rows]], 1).astype(np.int32)
+    used = False
+    if mutual:
+        back = _ops.feature_match(tf, sf)[0].cpu().numpy()
+        both = corr[back[corr[:, 1]] == corr[:, 0]]
+        if len(both) >= 3:
+            corr, used = both, True
+    if len(corr) < 3:
+        raise RuntimeError("register_points_global: fewer than 3 correspondences")
+    transform, report = _ops.ransac_transform(torch.from_numpy(sp).to(dev), torch.from_numpy(tp).to(dev),
+                                              torch.from_numpy(np.ascontiguousarray(corr)).to(dev), max_distance, 0.9,
+                                              hypotheses, seed)
+    return transform, dict(report, correspondences=int(len(corr)), mutual_used=used)
+
+
+def register_points_global(source, target, source_normals=None, target_normals=None, voxel_size=None, feature_k=48,
+                           max_distance=None, hypotheses=100000, seed=0, mutual=True, refine=True):
+    """Not in the reference's module.  Registration of two scans that are NOT roughly aligned: a global
+    search for the pose by FPFH descriptors and RANSAC, refined by register_points.  Every stage runs on the GPU and is a
+    pure function of the arguments.
+      1. merge_points(cell_size=voxel_size) on both clouds; voxel_size None: 1.5 % of the diagonal of the target's bounding
+         box.  The cell used is the voxel size of an octree level (between voxel_size and twice it), per cloud;
+         'cell_size' reports the larger of the two.
+      2. normals as given, averaged by the merge; without them estimate_normals(k=16) on the merged cloud (points without a
+         usable estimate are dropped).  ESTIMATED normals get their sign per cloud from its highest point, so two scans
+         in different poses may get opposite signs, which the descriptors do not survive: when a cloud's normals were
+         estimated, steps 3 to 5 run a second time with the source's normals negated and the pose with more inliers is
+         kept (a tie: the first; 'normals_flipped' says which).  A cloud whose estimate falls into several separately
+         signed parts is not covered by that: give oriented normals then.
+      3. asr_hip.ops.knn_index(feature_k) and ops.point_fpfh on both; points without a descriptor are left out.
+      4. ops.feature_match source -> target and, with mutual, target -> source: the pairs that choose each other; if fewer
+         than 3 remain, all source -> target pairs are used ('mutual_used' False).
+      5. ops.ransac_transform(max_distance, edge_ratio 0.9, hypotheses, seed); max_distance None: 1.5 x the cell used.
+      6. with refine: register_points(source, target, target_normals, init=that transform) on the clouds as given.
+    The method does not resolve near-symmetric shapes: on a smooth surface with a partial overlap the search returned the
+    180-degree flip.  RuntimeError when no hypothesis passes the tests.
+    -> register_points' dict ('transform' f64 [4,4], 'fitness', 'rmse', 'iterations', 'converged', 'degenerate', 'pairs';
+    without refine the transform is RANSAC's and the other fields are 0 / False) plus 'global': {'cell_size',
+    'correspondences', 'mutual_used', 'normals_flipped', 'evaluated', 'best_hypothesis', 'inliers', 'transform' f64 [4,4]
+    (RANSAC's)}."""
+    source = _f32(source, "source", "[M,3]", 2, 3)
+    target = _f32(target, "target", "[N,3]", 2, 3)
+    if source_normals is not None:
+        source_normals = _f32(source_normals, "source_normals", "[M,3]", 2, 3)
+    if target_normals is not None:
+        target_normals = _f32(target_normals, "target_normals", "[N,3]", 2, 3)
+    _ops.check_global_register_arguments(source, target, source_normals, target_normals, voxel_size, feature_k,
+                                         max_distance, hypotheses, seed)
+    finite = target[np.isfinite(target).all(1)]
+    if len(finite) == 0:
+        raise ValueError("target has no finite point")
+    if voxel_size is None:
+        voxel_size = 0.015 * float(np.linalg.norm(finite.max(0).astype(np.float64) - finite.min(0).astype(np.float64)))
+        if not voxel_size > 0:
+            raise ValueError("the target's bounding box is a point: give voxel_size")
+    dev = torch.device("cuda")
+    s_cloud = _global_cloud(source, source_normals, voxel_size, feature_k, dev)
+    t_cloud = _global_cloud(target, target_normals, voxel_size, feature_k, dev)
+    cell = max(s_cloud["cell"], t_cloud["cell"])
+    if max_distance is None:
+        max_distance = 1.5 * cell
+    tp, tf = _global_descriptors(t_cloud, dev)
+    transform, report, flipped = None, None, False
+    for flip in (False, True) if s_cloud["estimated"] or t_cloud["estimated"] else (False,):
+        sp, sf = _global_descriptors(s_cloud, dev, flip)
+        try:
+            pose, rep = _global_pose(sp, sf, tp, tf, mutual, max_distance, hypotheses, seed, dev)
+        except (RuntimeError, ValueError):
+            if report is None:
+                raise
+            continue  # the second pass found nothing to work with: the first one's pose stands
+        if report is None or (pose is not None and (transform is None or rep["inliers"] > report["inliers"])):
+            transform, report, flipped = pose, rep, flip
+    if transform is None:
+        raise RuntimeError("register_points_global: no hypothesis passed the edge-length and degeneracy tests")
+    transform = np.vstack([transform, [0.0, 0.0, 0.0, 1.0]])
+    info = dict(report, cell_size=float(cell), normals_flipped=flipped, transform=transform)
+    if refine:
+        result = register_points(source, target, target_normals, init=transform)
+    else:
+        result = {"iterations": 0, "converged": False, "degenerate": False, "pairs": 0, "rmse": 0.0, "fitness": 0.0,
+                  "transform": transform.copy()}
+    result["global"] = info
+    return result
+
+
 def transform_points(points, transform, normals=None):
     """Applies a rigid transform (4x4 or 3x4, as register_points returns it) to points [N,3] with the arithmetic of the
     registration itself: every coordinate is ((R0 x + R1 y) + R2 z) + t in f64, rounded once to f32.  Normals are rotated

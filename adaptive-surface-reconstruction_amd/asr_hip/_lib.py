@@ -183,6 +183,20 @@ class IcpReport(ctypes.Structure):
     ]
 
 
+class RansacParams(ctypes.Structure):
+    _fields_ = [
+        ("max_distance", ctypes.c_float),
+        ("reserved", ctypes.c_int32),
+        ("edge_ratio", ctypes.c_double),
+        ("num_hypotheses", ctypes.c_int64),
+        ("seed", ctypes.c_uint64),
+    ]
+
+
+class RansacReport(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int64) for name in ("evaluated", "best_hypothesis", "inliers")]
+
+
 # every symbol declared in include/asr_hip.h (tests/test_abi.py checks the list against the header)
 EXPORTS = [
     "asr_hip_context_create", "asr_hip_context_destroy", "asr_hip_context_set_stream",
@@ -207,6 +221,7 @@ EXPORTS = [
     "asr_hip_points_merge_count", "asr_hip_points_merge_fill",
     "asr_hip_knn_index", "asr_hip_point_normals", "asr_hip_normals_orient",
     "asr_hip_icp_step", "asr_hip_icp_update", "asr_hip_register_points",
+    "asr_hip_point_fpfh", "asr_hip_feature_match", "asr_hip_ransac_transform",
     "asr_hip_implicit_build",
     "asr_hip_implicit_network", "asr_hip_implicit_aggregate", "asr_hip_implicit_forward", "asr_hip_implicit_get",
     "asr_hip_implicit_stage_ms", "asr_hip_implicit_query",
@@ -241,7 +256,8 @@ def load():
                           ("asr_shard_stats", ShardStats), ("asr_mesh_topology", MeshTopology),
                           ("asr_mesh_fill_report", MeshFillReport),
                           ("asr_points_merge_report", PointsMergeReport), ("asr_icp_sums", IcpSums),
-                          ("asr_icp_params", IcpParams), ("asr_icp_report", IcpReport)):
+                          ("asr_icp_params", IcpParams), ("asr_icp_report", IcpReport),
+                          ("asr_ransac_params", RansacParams), ("asr_ransac_report", RansacReport)):
             if lib.asr_hip_struct_size(name.encode()) != ctypes.sizeof(cls):
                 raise AsrHipError("ABI mismatch: struct %s has a different size in libasr_hip.so"
                                   % name)
@@ -276,7 +292,12 @@ def load():
         lib.asr_hip_icp_update.argtypes = [ctypes.POINTER(IcpSums), dp, dp, dp]
         lib.asr_hip_register_points.argtypes = [vp, ctypes.POINTER(OctreeFrame), vp, i64, vp, vp, i64,
                                                 ctypes.POINTER(IcpParams), dp, ctypes.POINTER(IcpReport)]
-        for name in ("asr_hip_icp_step", "asr_hip_icp_update", "asr_hip_register_points"):
+        lib.asr_hip_point_fpfh.argtypes = [vp, vp, vp, i64, vp, ctypes.c_int, vp, vp, vp]
+        lib.asr_hip_feature_match.argtypes = [vp, vp, i64, vp, i64, ctypes.c_int, vp, vp]
+        lib.asr_hip_ransac_transform.argtypes = [vp, vp, i64, vp, i64, vp, i64, ctypes.POINTER(RansacParams), dp,
+                                                 ctypes.POINTER(RansacReport)]
+        for name in ("asr_hip_icp_step", "asr_hip_icp_update", "asr_hip_register_points", "asr_hip_point_fpfh",
+                     "asr_hip_feature_match", "asr_hip_ransac_transform"):
             getattr(lib, name).restype = ctypes.c_int
         for name in ("asr_hip_mesh_edges_count", "asr_hip_mesh_edges_fill", "asr_hip_mesh_topology", "asr_hip_mesh_smooth",
                      "asr_hip_mesh_fill_holes_count", "asr_hip_mesh_fill_holes_fill", "asr_hip_points_merge_count",

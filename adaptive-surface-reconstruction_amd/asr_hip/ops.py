@@ -1317,6 +1317,156 @@ def register_points(frame, target, target_normals, source, max_distance, init=No
     return np.array(tt[:]).reshape(3, 4), out
 
 
+FPFH_DIM = 33
+FEATURE_MATCH_MAX_DIM = 64
+FEATURE_MATCH_TILE = 128  # rows of b per LDS tile (csrc/asr_common.h ASR_FEATURE_MATCH_TILE): the tests' tile edges
+RANSAC_MAX_HYPOTHESES = 2 ** 24
+RANSAC_REPORT = ("evaluated", "best_hypothesis", "inliers")
+
+
+def check_point_fpfh_arguments(points, normals, index):
+    """the shapes and ranges of point_fpfh, or ValueError; no GPU involved -> (n, k)"""
+    n, k = check_point_normals_arguments(points, index)
+    if _shape(normals) != (n, 3):
+        raise ValueError("normals must have shape [N,3]")
+    return n, k
+
+
+def point_fpfh(points, normals, index, return_spfh=False, return_ok=False):
+    """Fast point feature histograms over given neighbour lists (asr_hip_point_fpfh; the contract is in include/asr_hip.h):
+    index int32 [N,k] with 3 <= k <= 64, from knn_index or hand-made, entries -1 skipped.  33 bins, theta | alpha | phi of
+    PCL's Darboux frame, all in f64 from the f32 inputs in a fixed order: the same bits on every run.  A point without a
+    usable normal (zero or not finite) has zero rows and ok = False and is no neighbour of anyone; ok is also False where
+    no pair of the row is valid.  -> fpfh f32 [N,33][, spfh f32 [N,33]][, ok bool [N]]"""
+    n, k = check_point_fpfh_arguments(points, normals, index)
+    points = _dev(points, torch.float32)
+    normals = _dev(normals, torch.float32)
+    index = _dev(index, torch.int32)
+    dev = _same_device(points, normals, index)
+    fpfh = torch.empty((n, FPFH_DIM), dtype=torch.float32, device=dev)
+    spfh = torch.empty((n, FPFH_DIM), dtype=torch.float32, device=dev) if return_spfh else None
+    ok = torch.empty(n, dtype=torch.uint8, device=dev) if return_ok else None
+    context(dev).call("asr_hip_point_fpfh", ptr(points), ptr(normals), i64(n), ptr(index), k, ptr(fpfh), ptr(spfh), ptr(ok))
+    out = (fpfh,) + ((spfh,) if return_spfh else ()) + ((ok.bool(),) if return_ok else ())
+    return out if len(out) > 1 else fpfh
+
+
+def check_feature_match_arguments(a, b):
+    """the shapes and ranges of feature_match, or ValueError; no GPU involved -> (m, n, dim)"""
+    sa, sb = _shape(a), _shape(b)
+    if len(sa) != 2 or len(sb) != 2 or sa[1] != sb[1]:
+        raise ValueError("a and b must have the shapes [M,D] and [N,D]")
+    if not 1 <= sa[1] <= FEATURE_MATCH_MAX_DIM:
+        raise ValueError("the rows must have 1 to %d entries" % FEATURE_MATCH_MAX_DIM)
+    if not 1 <= sb[0] < 2 ** 31:
+        raise ValueError("1 <= N < 2^31 rows of b are required")
+    if sa[0] >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 rows of a")
+    return sa[0], sb[0], sa[1]
+
+
+def feature_match(a, b):
+    """The exact nearest row of b [N,D] for every row of a [M,D], 1 <= D <= 64 (asr_hip_feature_match): the squared
+    distance is s = 0; s = s + (a_c - b_c)^2 over c ascending in f32, the result the smallest (s, j) -- a brute-force
+    search's, ties to the smaller row.  A row of a that is not finite gets -1 / +inf, a row of b that is not finite is never
+    chosen.  -> (index int32 [M], squared distance f32 [M])"""
+    m, n, dim = check_feature_match_arguments(a, b)
+    a = _dev(a, torch.float32)
+    b = _dev(b, torch.float32)
+    dev = _same_device(a, b)
+    index = torch.empty(m, dtype=torch.int32, device=dev)
+    sqdist = torch.empty(m, dtype=torch.float32, device=dev)
+    context(dev).call("asr_hip_feature_match", ptr(a), i64(m), ptr(b), i64(n), dim, ptr(index), ptr(sqdist))
+    return index, sqdist
+
+
+def check_ransac_arguments(source, target, corr, max_distance, edge_ratio=0.9, hypotheses=100000, seed=0):
+    """the shapes and ranges of ransac_transform, or ValueError; no GPU involved -> (m, n, c)"""
+    import math
+    import numpy as np
+    for name, t in (("source", source), ("target", target)):
+        shape = _shape(t)
+        if len(shape) != 2 or shape[1] != 3:
+            raise ValueError("%s must have shape [N,3]" % name)
+        if not 1 <= shape[0] < 2 ** 31:
+            raise ValueError("1 <= N < 2^31 %s points are required" % name)
+    shape = _shape(corr)
+    if len(shape) != 2 or shape[1] != 2:
+        raise ValueError("corr must have shape [C,2]")
+    if not 3 <= shape[0] < 2 ** 31:
+        raise ValueError("3 <= C < 2^31 correspondences are required")
+    try:
+        cap = float(np.float32(max_distance))
+    except (TypeError, ValueError):
+        raise ValueError("max_distance must be a number")
+    if not (math.isfinite(cap) and cap > 0.0):
+        raise ValueError("max_distance must be finite and > 0 (as a float32)")
+    try:
+        good = 0.0 < float(edge_ratio) <= 1.0
+    except (TypeError, ValueError):
+        good = False
+    if not good:
+        raise ValueError("edge_ratio must be a number in (0, 1]")
+    _check_int(hypotheses, 1, RANSAC_MAX_HYPOTHESES, "hypotheses")
+    _check_int(seed, 0, 2 ** 64 - 1, "seed")
+    return _shape(source)[0], _shape(target)[0], shape[0]
+
+
+def ransac_transform(source, target, corr, max_distance, edge_ratio=0.9, hypotheses=100000, seed=0):
+    """RANSAC over given correspondences (asr_hip_ransac_transform; the contract is in include/asr_hip.h): corr int32 [C,2]
+    of (source row, target row).  Hypothesis h draws three correspondences by splitmix64 of (seed, h), is rejected when two
+    coincide, when an edge of the source triangle and its partner differ by more than edge_ratio, or when a triangle is
+    degenerate; otherwise the rigid motion that maps one triangle's frame onto the other's is scored by the number of
+    correspondences it brings within max_distance.  The best score wins, ties go to the smallest h: a pure function of
+    the arguments.  -> (transform f64 [3,4], or None when no hypothesis passed, dict(evaluated, best_hypothesis, inliers))"""
+    import numpy as np
+    m, n, c = check_ransac_arguments(source, target, corr, max_distance, edge_ratio, hypotheses, seed)
+    source = _dev(source, torch.float32)
+    target = _dev(target, torch.float32)
+    corr = _dev(corr, torch.int32)
+    dev = _same_device(source, target, corr)
+    params = _lib.RansacParams(float(max_distance), 0, float(edge_ratio), int(hypotheses), int(seed))
+    report = _lib.RansacReport()
+    tt = (ctypes.c_double * 12)()
+    ctx = context(dev)
+    rc = ctx.lib.asr_hip_ransac_transform(ctx._h, ptr(source), i64(m), ptr(target), i64(n), ptr(corr), i64(c),
+                                          ctypes.byref(params), tt, ctypes.byref(report))
+    out = {name: int(getattr(report, name)) for name in RANSAC_REPORT}
+    if rc == 1 and not ctx.lib.asr_hip_last_error(ctx._h):  # no hypothesis passed: no error text
+        return None, out
+    ctx.check(rc)
+    return np.array(tt[:]).reshape(3, 4), out
+
+
+def check_global_register_arguments(source, target, source_normals=None, target_normals=None, voxel_size=None,
+                                    feature_k=48, max_distance=None, hypotheses=100000, seed=0):
+    """the shapes and ranges of register_points_global, or ValueError; no GPU involved -> (m, n)"""
+    import math
+    shapes = []
+    for name, t, nrm in (("source", source, source_normals), ("target", target, target_normals)):
+        shape = _shape(t)
+        if len(shape) != 2 or shape[1] != 3:
+            raise ValueError("%s must have shape [N,3]" % name)
+        if not 3 <= shape[0] < 2 ** 31:
+            raise ValueError("3 <= N < 2^31 %s points are required" % name)
+        if nrm is not None and _shape(nrm) != shape:
+            raise ValueError("%s_normals must have shape [N,3]" % name)
+        shapes.append(shape[0])
+    for name, v in (("voxel_size", voxel_size), ("max_distance", max_distance)):
+        if v is None:
+            continue
+        try:
+            good = math.isfinite(float(v)) and float(v) > 0.0
+        except (TypeError, ValueError):
+            good = False
+        if not good:
+            raise ValueError("%s must be a positive number" % name)
+    _check_int(feature_k, 3, KNN_INDEX_MAX_K, "feature_k")
+    _check_int(hypotheses, 1, RANSAC_MAX_HYPOTHESES, "hypotheses")
+    _check_int(seed, 0, 2 ** 64 - 1, "seed")
+    return shapes[0], shapes[1]
+
+
 def decode_mlp_at(code, shifts, w1, b1, w2, b2, w3, rows=None, voxel_sizes=None, gradient=False):
     """UNet5.decode(shifts, code[rows]) (net_definitions_torch.py:655-666) -> values [M,2]; with gradient=True
     (values, grad [M,3]) where grad is decode_with_gradient's d values[:,0] / d shift (:668-686, unscaled).

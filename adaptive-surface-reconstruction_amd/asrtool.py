@@ -8,6 +8,7 @@ reference (cpp/bin/main.cpp:114-177: `asrtool --in point_cloud.ply --out mesh.pl
     python adaptive-surface-reconstruction_amd/asrtool.py --thin-cloud scan.ply out.ply --cell SIZE
     python adaptive-surface-reconstruction_amd/asrtool.py --orient-cloud raw.ply out.ply [--k K] [--viewpoint x,y,z]
     python adaptive-surface-reconstruction_amd/asrtool.py --register source.ply target.ply out.ply [--max-distance D] [--iterations N] [--point-to-point]
+    python adaptive-surface-reconstruction_amd/asrtool.py --register source.ply target.ply out.ply --global [--voxel S] [--hypotheses N] [--seed K] [--max-distance D]
     python adaptive-surface-reconstruction_amd/asrtool.py --compare mesh.ply reference.ply [--samples N] [--thresholds a,b,...] [--seed S]
     python adaptive-surface-reconstruction_amd/asrtool.py --decimate mesh.ply out.ply --cell SIZE
     python adaptive-surface-reconstruction_amd/asrtool.py --smooth-mesh mesh.ply out.ply [--iterations N] [--boundary free|pinned|along]
@@ -57,6 +58,15 @@ Options:
     --max-distance D  --register: pairs further apart than D are ignored (default: 5 % of TARGET's bounding-box diagonal)
     --iterations N  --register: at most N iterations (default 50, 1 <= N <= 1000)
     --point-to-point  --register: ignores TARGET's normals
+    --global  --register: for scans that are NOT roughly aligned: first searches the pose by FPFH descriptors and RANSAC on
+              both clouds thinned to --voxel, then refines it by ICP with its defaults; the JSON line gains "global"
+              (cell_size, correspondences, mutual_used, normals_flipped, evaluated, best_hypothesis, inliers and RANSAC's
+              transform).  Normals of the files are used where present, else estimated (the search then also runs with
+              SOURCE's negated and keeps the better pose).  Does not resolve near-symmetric shapes
+    --voxel S  --register --global: cell of the thinning (default: 1.5 % of TARGET's bounding-box diagonal);
+              --max-distance D is then RANSAC's inlier distance (default: 1.5 x the cell used)
+    --hypotheses N  --register --global: RANSAC hypotheses (default 100000, 1 <= N <= 16777216)
+    --seed K  --register --global: seed of the draws (default 0); the result is a function of the inputs and K alone
     --thin-cloud IN.ply OUT.ply --cell SIZE  Instead of reconstructing: writes the cloud merged as --thin SIZE does, with its
               normals and, where the input has them, radii and colours; prints the cell size used
     --fill-mesh MESH.ply OUT.ply --max-edges N  Instead of reconstructing: closes the holes of at most N edges of an existing
@@ -280,8 +290,9 @@ def _orient_cloud(argv):
 
 
 def _register(argv):
-    """--register SOURCE.ply TARGET.ply OUT.ply [--max-distance D] [--iterations N] [--point-to-point]: one JSON line, 0;
-    a message on stderr and 1 (before any GPU work) when something is wrong"""
+    """--register SOURCE.ply TARGET.ply OUT.ply [--max-distance D] [--iterations N] [--point-to-point], or with --global
+    [--voxel S] [--hypotheses N] [--seed K] [--max-distance D]: one JSON line, 0; a message on stderr and 1 (before any GPU
+    work) when something is wrong"""
     import json
     i = argv.index("--register")
     paths = argv[i + 1:i + 4]
@@ -303,6 +314,35 @@ def _register(argv):
         if not 1 <= iterations <= 1000:
             sys.stderr.write("asrtool: --register: --iterations takes a number N, 1 <= N <= 1000\n")
             return 1
+    search = "--global" in argv
+    voxel, hypotheses, seed = None, 100000, 0
+    if search:
+        for name in ("--iterations", "--point-to-point"):
+            if name in argv:
+                sys.stderr.write("asrtool: --register --global: %s does not apply (the refinement runs with its defaults)\n"
+                                 % name)
+                return 1
+        if "--voxel" in argv:
+            voxel = _size(_option(argv, "--voxel"))
+            if voxel is None:
+                sys.stderr.write("asrtool: --register --global: --voxel takes a positive number S\n")
+                return 1
+        if "--hypotheses" in argv:
+            try:
+                hypotheses = int(_option(argv, "--hypotheses"))
+            except (TypeError, ValueError):
+                hypotheses = 0
+            if not 1 <= hypotheses <= 2 ** 24:
+                sys.stderr.write("asrtool: --register --global: --hypotheses takes a number N, 1 <= N <= 16777216\n")
+                return 1
+        if "--seed" in argv:
+            try:
+                seed = int(_option(argv, "--seed"))
+            except (TypeError, ValueError):
+                seed = -1
+            if not 0 <= seed < 2 ** 64:
+                sys.stderr.write("asrtool: --register --global: --seed takes a number K, 0 <= K < 2^64\n")
+                return 1
     for p in paths[:2]:
         if not os.path.isfile(p):
             sys.stderr.write("asrtool: --register: no such file: %s\n" % p)
@@ -325,11 +365,25 @@ def _register(argv):
         return 1
     has = lambda a: a is not None and len(a) == len(target)  # noqa: E731
     plane = has(target_normals) and "--point-to-point" not in argv
+    if search and min(len(source), len(target)) < 3:
+        sys.stderr.write("asrtool: --register --global: both clouds need at least 3 points\n")
+        return 1
     if not plane and "--point-to-point" not in argv:
         sys.stderr.write("asrtool: --register: %s has no normals, using point-to-point\n" % paths[1])
     import adaptivesurfacereconstruction as asr
-    result = asr.register_points(source, target, target_normals if plane else None, max_distance=max_distance,
-                                 max_iterations=iterations)
+    if search:
+        own = source_normals if source_normals is not None and len(source_normals) == len(source) else None
+        try:
+            result = asr.register_points_global(source, target, own, target_normals if plane else None, voxel_size=voxel,
+                                                max_distance=max_distance, hypotheses=hypotheses, seed=seed)
+        except (RuntimeError, ValueError) as e:
+            sys.stderr.write("asrtool: --register --global: %s\n" % e)
+            return 1
+        info = result.pop("global")
+        result["global"] = dict(info, transform=[[float(x) for x in row] for row in info["transform"]])
+    else:
+        result = asr.register_points(source, target, target_normals if plane else None, max_distance=max_distance,
+                                     max_iterations=iterations)
     transform = result.pop("transform")
     if source_normals is not None and len(source_normals) == len(source):
         moved, moved_normals = asr.transform_points(source, transform, source_normals)

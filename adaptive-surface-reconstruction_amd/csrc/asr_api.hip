@@ -112,6 +112,8 @@ size_t asr_hip_struct_size(const char* name) {
     if (!strcmp(name, "asr_icp_sums")) return sizeof(asr_icp_sums);
     if (!strcmp(name, "asr_icp_params")) return sizeof(asr_icp_params);
     if (!strcmp(name, "asr_icp_report")) return sizeof(asr_icp_report);
+    if (!strcmp(name, "asr_ransac_params")) return sizeof(asr_ransac_params);
+    if (!strcmp(name, "asr_ransac_report")) return sizeof(asr_ransac_report);
     return 0;
 }
 
@@ -2036,6 +2038,41 @@ int asr_hip_implicit_stage_ms(asr_hip_context* ctx, float out_ms[8]) {
         out_ms[2] = ms;
     }
     return ASR_HIP_OK;
+}
+
+int asr_hip_point_fpfh(asr_hip_context* ctx, const float* points, const float* normals, int64_t n, const int32_t* index,
+                       int k, float* fpfh_out, float* spfh_out, uint8_t* ok_out) {
+    CTX_GUARD(ctx);
+    if (n < 0 || n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "point_fpfh: 0 <= n < 2^31 points are required");
+    if (k < 3 || k > 64) ASR_FAIL(ctx, ASR_HIP_EINVAL, "point_fpfh: k = %d is not in 3..64", k);
+    if (n > 0 && (!points || !normals || !index || !fpfh_out)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "point_fpfh: null argument");
+    return asr_features_fpfh(ctx, points, normals, n, index, k, fpfh_out, spfh_out, ok_out);
+}
+int asr_hip_feature_match(asr_hip_context* ctx, const float* a, int64_t m, const float* b, int64_t n, int dim,
+                          int32_t* index_out, float* sqdist_out) {
+    CTX_GUARD(ctx);
+    if (n < 1 || n >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "feature_match: 1 <= n < 2^31 rows of b are required");
+    if (m < 0 || m >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "feature_match: 0 <= m < 2^31 rows of a are required");
+    if (dim < 1 || dim > 64) ASR_FAIL(ctx, ASR_HIP_EINVAL, "feature_match: dim = %d is not in 1..64", dim);
+    if (!b || (m > 0 && !a)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "feature_match: null argument");
+    return asr_features_match(ctx, a, m, b, n, dim, index_out, sqdist_out);
+}
+int asr_hip_ransac_transform(asr_hip_context* ctx, const float* source, int64_t m, const float* target, int64_t n,
+                             const int32_t* corr, int64_t c, const asr_ransac_params* params, double transform_out[12],
+                             asr_ransac_report* report) {
+    CTX_GUARD(ctx);
+    if (!source || !target || !corr || !params || !transform_out || !report)
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "ransac_transform: null argument");
+    if (m < 1 || m >= (i64(1) << 31) || n < 1 || n >= (i64(1) << 31))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "ransac_transform: 1 <= m, n < 2^31 points are required");
+    if (c < 3 || c >= (i64(1) << 31)) ASR_FAIL(ctx, ASR_HIP_EINVAL, "ransac_transform: 3 <= c < 2^31 correspondences are required");
+    if (!std::isfinite(params->max_distance) || !(params->max_distance > 0.f))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "ransac_transform: max_distance must be finite and > 0");
+    if (!(params->edge_ratio > 0.0) || !(params->edge_ratio <= 1.0))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "ransac_transform: edge_ratio must be in (0, 1]");
+    if (params->num_hypotheses < 1 || params->num_hypotheses > (i64(1) << 24))
+        ASR_FAIL(ctx, ASR_HIP_EINVAL, "ransac_transform: num_hypotheses must be in 1..2^24");
+    return asr_features_ransac(ctx, source, m, target, n, corr, c, params, transform_out, report);
 }
 
 }  // extern "C"

@@ -582,6 +582,16 @@ int asr_points_normals(asr_hip_context* ctx, const float* points, i64 n, const i
 int asr_points_orient(asr_hip_context* ctx, const float* points, const float* normals, i64 n, const int32_t* index, int k,
                       const float* viewpoints, i64 num_viewpoints, float* normals_out, uint8_t* flips_out, i64 report[4]);
 
+// Global registration (asr_hip_point_fpfh / _feature_match / _ransac_transform, asr_features.hip); arguments validated by
+// the callers.  ASR_FEATURE_MATCH_TILE: rows of b per LDS tile of the match (asr_hip.ops.FEATURE_MATCH_TILE for the tests).
+#define ASR_FEATURE_MATCH_TILE 128
+int asr_features_fpfh(asr_hip_context* ctx, const float* points, const float* normals, i64 n, const int32_t* index, int k,
+                      float* fpfh_out, float* spfh_out, uint8_t* ok_out);
+int asr_features_match(asr_hip_context* ctx, const float* a, i64 m, const float* b, i64 n, int dim, int32_t* index_out,
+                       float* sqdist_out);
+int asr_features_ransac(asr_hip_context* ctx, const float* source, i64 m, const float* target, i64 n, const int32_t* corr,
+                        i64 c, const asr_ransac_params* params, double transform_out[12], asr_ransac_report* report);
+
 int asr_conv_agg_importance(asr_hip_context* ctx, const float* compat, const float* dist, i64 n,
                             float* out);
 int asr_conv_cconv(asr_hip_context* ctx, const float* filters, const float* out_pos,

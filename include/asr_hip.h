@@ -24,7 +24,8 @@
  *   calls of the grid_neighbors and grid_coarsen pairs, the octree builds and the asr_hip_implicit_* entry points, and
  *   every single-call operator that needs device temporaries (the searches: knn_*, radius_neighbor_count,
  *   nearest_point, point_attributes_at, icp_step, register_points; row_groups, invert_neighbors_list, sparse_conv_plan_create,
- *   continuous_conv_f32; mesh_sample, mesh_topology, mesh_smooth; normals_orient).  Take every call that enqueues work
+ *   continuous_conv_f32; mesh_sample, mesh_topology, mesh_smooth; normals_orient; point_fpfh, feature_match,
+ *   ransac_transform).  Take every call that enqueues work
  *   on the context for one of them; the calls that only read or set host state (last_error, options, set_stream, ...)
  *   never are.  The input arrays of X_count must stay alive and unchanged until X_fill returns: fill reads them again.
  *
@@ -819,6 +820,92 @@ int asr_hip_icp_update(const asr_icp_sums* sums, const double origin[3], double 
 int asr_hip_register_points(asr_hip_context* ctx, const asr_octree_frame* frame, const float* target_dev, int64_t n,
                             const float* target_normals_dev, const float* source_dev, int64_t m,
                             const asr_icp_params* params, double transform_inout[12], asr_icp_report* report);
+
+/* ---- global registration: FPFH descriptors, nearest descriptors, RANSAC (not in the reference) -------- */
+/* The borders of the theta bins: (cos beta_b, sin beta_b), beta_b = -pi + 2 pi b / 11, b = 1..10, as f64 literals.  The
+ * numpy restatement (tests/global_register_ref.py) carries the same literals. */
+#define ASR_FPFH_BINS 11
+#define ASR_FPFH_DIM 33
+#define ASR_FPFH_THETA_TABLE                               \
+    {                                                      \
+        {-0.84125353283118109, -0.54064081745559778},      \
+        {-0.41541501300188632, -0.90963199535451844},      \
+        {0.14231483827328512, -0.98982144188093268},       \
+        {0.6548607339452851, -0.75574957435425827},        \
+        {0.95949297361449748, -0.2817325568414295},        \
+        {0.95949297361449748, 0.2817325568414295},         \
+        {0.6548607339452851, 0.75574957435425827},         \
+        {0.14231483827328512, 0.98982144188093268},        \
+        {-0.41541501300188616, 0.90963199535451855},       \
+        {-0.84125353283118132, 0.54064081745559744},       \
+    }
+/* Fast point feature histograms over given lists.  points_dev, normals_dev f32 [n,3]; index_dev int32 [n,k], 3 <= k <= 64,
+ * from asr_hip_knn_index or hand-made: entries equal to -1 are skipped, any other entry outside [0, n) is ASR_HIP_EINVAL
+ * (checked on the device).  fpfh_out_dev f32 [n,33]; spfh_out_dev f32 [n,33] and ok_out_dev u8 [n] may be NULL.
+ * All arithmetic is f64 from the f32 inputs, uncontracted, only + - * / sqrt; a sum of three products is (a + b) + c.
+ *   Normals: nn = (nx nx + ny ny) + nz nz; a normal is USABLE when its components are finite and nn > 0, and is then used
+ *     as n / sqrt(nn).  A point without a usable normal has ok = 0 and zero rows and is no neighbour of anyone.
+ *   Pair (i, slot s), j = index[i,s]: d = p_j - p_i, d2 = (dx dx + dy dy) + dz dz, dist = sqrt(d2).  The pair is NEAR when
+ *     j is neither -1 nor i, both normals are usable and 0 < dist < +inf.  a1 = n_i . d, a2 = n_j . d.  Darboux frame as in
+ *     PCL: if |a1| < |a2|: u = n_j, n_t = n_i, d <- -d, phi = -a2 / dist; otherwise u = n_i, n_t = n_j, phi = a1 / dist.
+ *     c = d x u (cx = dy uz - dz uy, ...), |c| = sqrt(c . c); the pair is VALID when it is near and |c| > 0.  v = c / |c|,
+ *     w = u x v, alpha = v . n_t, x = u . n_t, y = w . n_t.
+ *   Bins, 11 per feature, in the order theta | alpha | phi.  alpha and phi: clamp(floor((f + 1) * 5.5), 0, 10).  theta,
+ *     the bin of atan2(y, x), without a transcendental function: with (cos_b, sin_b) of ASR_FPFH_THETA_TABLE and
+ *     y'_b = y cos_b - x sin_b, ge_b = (y >= 0) || (y'_b >= 0) for b <= 5 and (y >= 0) && (y'_b >= 0) for b >= 6;
+ *     bin = the number of b in 1..10 with ge_b.
+ *   SPFH: spfh[i][b] = (float)((100.0 * count_b) / m) over the m valid pairs of row i; m = 0 gives zeros and ok = 0.
+ *   FPFH (Open3D's form): acc[b] = sum over the NEAR slots of row i, in slot order, of (double)spfh[j][b] / d2.  Each of
+ *     the three sub-histograms: total = its acc added over b ascending, scaled[b] = (100.0 * acc[b]) / total, or 0 when the
+ *     total is 0.  fpfh[i][b] = (float)(scaled[b] + (double)spfh[i][b]).
+ * Plain stores, no atomics on values: the same bits on every run.  Two launches and one read-back (the index check);
+ * when spfh_out_dev is NULL the SPFH rows live in the context's scratch arena, which the call recycles either way. */
+int asr_hip_point_fpfh(asr_hip_context* ctx, const float* points_dev, const float* normals_dev, int64_t n,
+                       const int32_t* index_dev, int k, float* fpfh_out_dev, float* spfh_out_dev, uint8_t* ok_out_dev);
+/* The exact nearest row of b_dev (f32 [n,dim]) for every row of a_dev (f32 [m,dim]); 1 <= dim <= 64, 1 <= n < 2^31,
+ * 0 <= m < 2^31.  Per pair of rows, in f32 without contraction: s = 0; for c ascending: t = a_c - b_c; s = s + t * t.
+ * The result is the smallest pair (s, j): ties go to the smaller j, as in a brute-force search.  A row of a with a
+ * non-finite entry gets index -1 and distance +inf; a row of b with one is never chosen; without any usable row of b every
+ * result is -1 / +inf.  index_out_dev int32 [m], sqdist_out_dev f32 [m]; either may be NULL.  The rows of b may be split
+ * over workgroups, whose partial results meet in a 64-bit atomicMin of bits(s) << 32 | j: the result does not depend on
+ * the order.  Recycles the scratch arena; not waited for. */
+int asr_hip_feature_match(asr_hip_context* ctx, const float* a_dev, int64_t m, const float* b_dev, int64_t n, int dim,
+                          int32_t* index_out_dev, float* sqdist_out_dev);
+typedef struct asr_ransac_params {
+    float max_distance;     /* an inlier's cap: finite, > 0                                   */
+    int32_t reserved;
+    double edge_ratio;      /* 0 < r <= 1: both edge lengths of a triple within that ratio     */
+    int64_t num_hypotheses; /* 1 <= H <= 2^24                                                  */
+    uint64_t seed;
+} asr_ransac_params;
+typedef struct asr_ransac_report {
+    int64_t evaluated;       /* hypotheses that passed the tests and were scored               */
+    int64_t best_hypothesis; /* -1 when none passed                                            */
+    int64_t inliers;         /* of the best one                                                */
+} asr_ransac_report;
+/* RANSAC over given correspondences: hypotheses from triples, each scored over all correspondences.  source_dev f32 [m,3],
+ * target_dev f32 [n,3], corr_dev int32 [c,2] of (source row, target row), 3 <= c < 2^31; a row outside its cloud is
+ * ASR_HIP_EINVAL (checked on the device).  A correspondence with a non-finite point is never an inlier, and a triple with
+ * one is rejected.
+ *   Hypothesis h = 0 .. H-1, draw r = 0, 1, 2 (splitmix64, u64 wrap-around):
+ *     z = seed + (3h + r + 1) * 0x9E3779B97F4A7C15;  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^= z >> 31;  draw = ((z >> 32) * c) >> 32.
+ *   Rejected when two draws coincide, when for one of the edges (0,1), (0,2), (1,2) the f64 lengths ls (source) and lt
+ *     (target), sqrt((dx dx + dy dy) + dz dz), fail ls >= r lt or lt >= r ls, or when a frame is degenerate.
+ *   Frame of three points, f64: e1 = (p1 - p0) / |p1 - p0|, g = e1 x (p2 - p0), e3 = g / |g|, e2 = e3 x e1; degenerate
+ *     unless both norms are > 0.  R[a][b] = (Ft[a][0] Fs[b][0] + Ft[a][1] Fs[b][1]) + Ft[a][2] Fs[b][2] with the columns
+ *     e1, e2, e3; t[a] = t0[a] - ((R[a][0] s0x + R[a][1] s0y) + R[a][2] s0z), anchored at the first pair.
+ *   Score: the number of correspondences whose source point, moved as asr_hip_icp_step moves it (f64, rounded once to
+ *     f32), has d2 = ((dx dx + dy dy) + dz dz) <= cap2 = max_distance * max_distance to its partner, both in f32.
+ *   The winner is the largest score, ties go to the smallest h (a 64-bit atomicMax of score << 32 | ~h): integers only,
+ *     no summation order enters.
+ * transform_out: 12 doubles, the rows of (R | t).  Returns 0; or 1 = no hypothesis passed, with transform_out untouched
+ * and the report {0, -1, 0} -- the code ASR_HIP_EINVAL has too, told apart by asr_hip_last_error(), which is then empty.
+ * ASR_HIP_EINVAL: sizes, a NULL argument, max_distance not finite or <= 0, edge_ratio outside (0, 1], H outside 1..2^24.
+ * Recycles the scratch arena.  Two read-backs: the number of survivors, which shapes the scoring launch, and the result. */
+int asr_hip_ransac_transform(asr_hip_context* ctx, const float* source_dev, int64_t m, const float* target_dev, int64_t n,
+                             const int32_t* corr_dev, int64_t c, const asr_ransac_params* params, double transform_out[12],
+                             asr_ransac_report* report);
 /* (asr_hip_implicit_query, the whole-path query on the last forward, is declared after asr_hip_implicit_stage_ms) */
 
 /* ---- whole path: the section of asr::ReconstructSurface between the pre-filter and the
